@@ -2,6 +2,7 @@
 """bench.py -- RNNPose recurrent pose-refinement throughput on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
     python bench.py --gpus 8                       # no WORLD_SIZE in the environment: spawns the 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -44,6 +45,8 @@ sys.path.insert(0, ROOT)
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s measured achievable)
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 peak
 PEAK_F16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense fp16/bf16 MFMA peak (no sparsity)
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all arrays together, .npy headers included
+DUMP_SAMPLE_SEED = 0
 
 
 def parse():
@@ -68,12 +71,58 @@ def parse():
     ap.add_argument("--workload", choices=["cfg1", "cfg4"], default=None,
                     help="a BASELINE.json configuration verbatim: cfg1 = configs[1] (640x480, batch 8/GPU, 3x8: the default), cfg4 = "
                          "configs[4] (1280x960 high-res, batch 8/GPU = batch 64 over 8 GPUs, 3x8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10**6} MB in all: larger outputs are stored as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.workload == "cfg4":
         args.batch, args.height, args.width, args.outer, args.inner = 8, 960, 1280, 3, 8
     elif args.workload == "cfg1":
         args.batch, args.height, args.width, args.outer, args.inner = 8, 480, 640, 3, 8
     return args
+
+
+def step_outputs(out):
+    """The arrays a caller of PoseRefiner.forward receives from one step, by name (the echoed inputs -- intrinsics, views --
+    are left out).  Floating-point tensors keep float64 or become float32; masks and counters become float64/float32 numbers."""
+    arrays = {"Ti_pred": out["Ti_pred"].G, "Tij": out["Tij"].G}
+    for i, f in enumerate(out["flow"]):
+        arrays[f"flow_{i}"] = f
+    arrays.update(flow_last=out["flow_last"], weight=out["weight"], vmask=out["vmask"], f16x3_range_events=out["f16x3_range_events"])
+    res = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        res[name] = a if a.dtype == "float64" else a.astype("float64" if a.dtype.kind in "iu" else "float32")
+    return res
+
+
+def dump_outputs(arrays, path, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """Write every array as path/<name>.npy.  If they do not fit in `limit` bytes together, every array larger than 1 MB is
+    replaced by the same fraction of its elements, flattened, at positions drawn once from a generator seeded with `seed` and
+    the array's size (sorted): the sample depends only on the arguments, so two builds' dumps compare element for element.
+    -> {name: {"shape", "dtype", "sampled"}}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    header = 256                                                       # bound on one .npy header (128 bytes for these shapes)
+    big = {k for k, a in arrays.items() if a.nbytes > 2**20}
+    fixed = sum(a.nbytes + header for k, a in arrays.items() if k not in big) + header * len(big)
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    frac = 1.0 if fixed + big_bytes <= limit else max(0.0, (limit - fixed) / big_bytes)
+    info = {}
+    for name, a in arrays.items():
+        sampled = name in big and frac < 1.0
+        if sampled:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.default_rng([seed, a.size]).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": list(arrays[name].shape), "dtype": str(a.dtype), "sampled": (f"{a.size} of {arrays[name].size} elements"
+                                                                                          if sampled else None)}
+    return info
 
 
 def spawn_ranks(n):
@@ -300,12 +349,12 @@ def main():
     # HIP events bracket every C-ABI launch of the FIRST OUTER ITERATION of the first timed step only (~450 launches,
     # eager): the rest of that step and the other K-1 steps replay hipGraphs, so that a small K does not dilute `value`.
     rec = refiner.profile_first_outer() if (args.outer > 1 and not args.unfused) else ops.profile_begin(None)
-    step()
+    out = step()
     if refiner.profile_rec is not None or ops.profiling():      # single outer iteration / unfused: the whole step was recorded
         ops.profile_end(rec)
         refiner.profile_rec = None
     for _ in range(args.steps - 1):
-        step()
+        out = step()
     torch.cuda.synchronize()
     D.barrier()
     dt_rank = time.perf_counter() - t0
@@ -317,6 +366,9 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:
+        info = dump_outputs(step_outputs(out), args.dump_outputs)
+        print(f"bench.py: last timed step's outputs -> {args.dump_outputs}: {json.dumps(info)}", file=sys.stderr)
     iters = args.outer * args.inner
     value = world * args.steps * iters / dt
     ms_step = dt / args.steps * 1e3

@@ -97,19 +97,24 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def _build_locked(dig: str, verbose: bool) -> str:
+    from concurrent.futures import ThreadPoolExecutor
     objs = []
-    procs = []
+    cmds = []
     for src in sources():
         obj = os.path.join(LIBDIR, os.path.basename(src) + ".o")
         cmd = [hipcc(), "-c", "-x", "hip", src, "-o", obj, "-I", os.path.join(ROOT, "include"), "-I", CSRC] + \
               [f for f in FLAGS if f != "-shared"] + PER_FILE_FLAGS.get(os.path.basename(src), [])
         if verbose:
             print(" ".join(cmd))
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+        cmds.append((src, cmd))
         objs.append(obj)
+    jobs = max(1, int(os.environ.get("MAX_JOBS") or 16))          # at most 16 compilers at once unless MAX_JOBS says otherwise
+    run = lambda c: subprocess.run(c, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    with ThreadPoolExecutor(jobs) as pool:
+        results = list(zip([src for src, _ in cmds], pool.map(run, [cmd for _, cmd in cmds])))
     failed = False
-    for src, p in procs:
-        out, _ = p.communicate()
+    for src, p in results:
+        out = p.stdout
         if p.returncode != 0:
             failed = True
             sys.stderr.write(f"--- hipcc failed on {src}\n{out}\n")

@@ -14,7 +14,13 @@ def _free_port():
     return p
 
 
+def _host_only():
+    """A gloo rank of the host tests stays off the GPU: on a GPU box init_from_env would otherwise bind every rank to a device."""
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, n_items, q):
+    _host_only()
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     from rnnpose_amd import distributed as D
@@ -82,10 +88,12 @@ import pytest  # noqa: E402
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="the RCCL path needs two devices (one rank per GPU): first executed by the driver's multi-GPU run")
 def test_two_rank_rccl_on_two_devices():
     """The `nccl` (= RCCL) branch of distributed.init_from_env on real devices: one rank per GPU, device-bound communicator, the
-    packed metric all_reduce(SUM), the MAX clock, ranks_seen.  Skipped on single-GPU boxes (every gpurun lease of this build)."""
+    packed metric all_reduce(SUM), the MAX clock, ranks_seen.  Skipped on single-GPU boxes.  (The device count is asked here, not
+    in a skipif: a module-level query would open the GPU in every process that imports this module, the spawned host ranks too.)"""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("the RCCL path needs two devices (one rank per GPU): first executed by the driver's multi-GPU run")
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
@@ -106,6 +114,7 @@ def _lazy_load_worker(rank, world, port, q):
     """What bench.py does on every rank, in bench.py's order: import the package and its ops BEFORE distributed.build_once.  The
     shared library must not be dlopen'ed by that (ranks > 0 would map a file rank 0 is still writing): _lib.load() is lazy."""
     import time
+    _host_only()
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from rnnpose_amd import distributed as D
     D.init_from_env(backend="gloo")

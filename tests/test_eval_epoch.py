@@ -76,6 +76,7 @@ def _free_port():
 
 
 def _cpu_worker(rank, world, port, q):
+    torch.cuda.is_available = lambda: False      # a host rank stays off the GPU (init_from_env would bind it to a device on a GPU box)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from rnnpose_amd import distributed as D
     D.init_from_env(backend="gloo")
