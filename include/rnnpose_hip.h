@@ -417,6 +417,24 @@ int rnnpose_flow_head_out_f32(const float* x, int x_c_stride, int x_c_offset, in
                               float* coords1_out, float* flow_lr, rnnpose_stream_t stream);
 int rnnpose_convex_upsample_nhwc_f32(const float* flow_lr, const float* mask, int B, int h, int w, float* flow_up,
                                      rnnpose_stream_t stream);
+/* ---- SuperPoint2D glue (model/descriptor2D.py; rnnpose_amd/descriptor2d.py) -------------------------------------------
+ * Channel windows [c_offset, +C) of NHWC tensors (B,H,W,c_stride): C, offsets and strides multiples of 4, 16-byte aligned
+ * tensors; B * H * W (of the larger side) below 2^31.
+ * maxpool2x2_nhwc: nn.MaxPool2d(2, 2) (floor): (B,H,W) -> (B,H/2,W/2), NaN propagating.
+ * upsample2x_bilinear_nhwc: nn.Upsample(scale_factor=2, mode='bilinear') (align_corners=False): (B,h,w) -> (B,2h,2w).
+ *   mean_rstd (B,C,2) of the source window or NULL: every tap is read as (x - mean) * rstd, then ReLU'd when relu != 0 (the
+ *   instance norm + ReLU of the decoder stages, applied in the load).
+ * pixel_head_nhwc: 1x1 convolution c_in (<= 256) -> c_out (<= 32) with weight (c_out, c_in) fp32 + bias, the source read as
+ *   relu?((x - mean) * rstd) when mean_rstd (B,c_in,2) is given (relu alone without it), written NCHW to dst (B,c_out,HW);
+ *   mode 0 linear, 1 L2 normalisation over the outputs (F.normalize: y / max(|y|_2, 1e-12)), 2 sigmoid. */
+int rnnpose_maxpool2x2_nhwc_f32(const float* src, int B, int H, int W, int src_c_stride, int src_c_offset, int C, float* dst,
+                                int dst_c_stride, int dst_c_offset, rnnpose_stream_t stream);
+int rnnpose_upsample2x_bilinear_nhwc_f32(const float* src, int B, int h, int w, int src_c_stride, int src_c_offset, int C,
+                                         const float* mean_rstd, int relu, float* dst, int dst_c_stride, int dst_c_offset,
+                                         rnnpose_stream_t stream);
+int rnnpose_pixel_head_nhwc_f32(const float* src, int B, int HW, int src_c_stride, int src_c_offset, int c_in,
+                                const float* mean_rstd, int relu, const float* weight, const float* bias, int c_out, int mode,
+                                float* dst_nchw, rnnpose_stream_t stream);
 /* 1x1 convolution (+ bias, optional ReLU) with the activation tile resident in LDS: 32 pixels x ALL 256 output columns per
  * workgroup, the tile split into fp16 hi / lo once (the implicit-GEMM kernel re-splits it per 64-column tile).  Used for
  * BasicMotionEncoder.convc1 (thirdparty/raft/update.py:80,87: 324 -> 256).  pack: weight (256, c_in) fp32 -> MFMA fragments

@@ -103,6 +103,9 @@ PROTOTYPES = {
     "rnnpose_flow_features_induced_f32": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _f, _p]),
     "rnnpose_corr_lookup_induced_nhwc_part_f32": (_i, [_p, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "rnnpose_split_hl_f32": (_i, [_p, _i, _i, _ll, _i, _f, _p, _i, _i, _p]),
+    "rnnpose_maxpool2x2_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p]),
+    "rnnpose_upsample2x_bilinear_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
+    "rnnpose_pixel_head_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
     "rnnpose_flow_head_out_f32": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "rnnpose_convex_upsample_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "rnnpose_mask_upsample_f16x3": (_i, [_p, _i, _i, _p, _i, _p, _f, _f, _p, _i, _i, _i, _p, _p]),

@@ -544,6 +544,191 @@ __global__ __launch_bounds__(256) void split_hl_kernel(const float* __restrict__
   *reinterpret_cast<rp::h8*>(o + 4) = rp::h8{l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
 }
 
+// ---- SuperPoint2D glue (model/descriptor2D.py): 2x2 max pooling, 2x bilinear up-sampling, the 1x1 output heads ----------
+// All three are memory-bound.  Pixel indices are 32-bit (the launchers refuse B*H*W >= 2^31), element offsets 64-bit.
+
+// nn.MaxPool2d(2, 2) (floor): one thread per output pixel and channel quad.  max propagates NaN as torch does.
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+
+__global__ __launch_bounds__(256) void maxpool2x2_nhwc_kernel(const float* __restrict__ src, int scs, int sco,
+                                                              float* __restrict__ dst, int dcs, int dco, int H, int W, int Ho,
+                                                              int Wo, int nq, long long total) {
+  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int q = static_cast<int>(t % nq);
+  const int m = static_cast<int>(t / nq);                      // output pixel (b, y, x)
+  const int x = m % Wo, y = (m / Wo) % Ho, b = m / (Wo * Ho);
+  const long long p00 = (static_cast<long long>(b) * H + 2 * y) * W + 2 * x;
+  const float* s = src + sco + 4 * q;
+  const float4 a = *reinterpret_cast<const float4*>(s + p00 * scs);
+  const float4 c = *reinterpret_cast<const float4*>(s + (p00 + 1) * scs);
+  const float4 d = *reinterpret_cast<const float4*>(s + (p00 + W) * scs);
+  const float4 e = *reinterpret_cast<const float4*>(s + (p00 + W + 1) * scs);
+  float4 r;
+  r.x = max_nan(max_nan(a.x, c.x), max_nan(d.x, e.x));
+  r.y = max_nan(max_nan(a.y, c.y), max_nan(d.y, e.y));
+  r.z = max_nan(max_nan(a.z, c.z), max_nan(d.z, e.z));
+  r.w = max_nan(max_nan(a.w, c.w), max_nan(d.w, e.w));
+  *reinterpret_cast<float4*>(dst + static_cast<long long>(m) * dcs + dco + 4 * q) = r;
+}
+
+// nn.Upsample(scale_factor=2, mode='bilinear', align_corners=False): source coordinate max(0, (o + 0.5) / 2 - 0.5), upper
+// neighbour clamped to the last row / column (PyTorch's upsample_bilinear2d).  With mean_rstd (B, C, 2) every tap is read as
+// relu?((x - mean) * rstd): the instance norm (+ ReLU) of the decoder stages is applied here instead of being materialised.
+__global__ __launch_bounds__(256) void upsample2x_bilinear_nhwc_kernel(const float* __restrict__ src, int scs, int sco,
+                                                                       const float* __restrict__ mean_rstd, int relu,
+                                                                       float* __restrict__ dst, int dcs, int dco, int h, int w,
+                                                                       int nq, long long total) {
+  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int H = 2 * h, W = 2 * w;
+  const int q = static_cast<int>(t % nq);
+  const int m = static_cast<int>(t / nq);                      // output pixel (b, oy, ox)
+  const int ox = m % W, oy = (m / W) % H, b = m / (W * H);
+  const float sy = fmaxf(0.f, (static_cast<float>(oy) + 0.5f) * 0.5f - 0.5f);
+  const float sx = fmaxf(0.f, (static_cast<float>(ox) + 0.5f) * 0.5f - 0.5f);
+  const int y0 = static_cast<int>(sy), x0 = static_cast<int>(sx);
+  const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+  const float ly1 = sy - static_cast<float>(y0), lx1 = sx - static_cast<float>(x0);
+  const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+  const int c = 4 * q;
+  const float* s = src + sco + c;
+  const long long rb = static_cast<long long>(b) * h;
+  float4 v[4] = {*reinterpret_cast<const float4*>(s + ((rb + y0) * w + x0) * scs),
+                 *reinterpret_cast<const float4*>(s + ((rb + y0) * w + x1) * scs),
+                 *reinterpret_cast<const float4*>(s + ((rb + y1) * w + x0) * scs),
+                 *reinterpret_cast<const float4*>(s + ((rb + y1) * w + x1) * scs)};
+  if (mean_rstd) {
+    const float4 s01 = *reinterpret_cast<const float4*>(mean_rstd + (static_cast<long long>(b) * (nq * 4) + c) * 2);
+    const float4 s23 = *reinterpret_cast<const float4*>(mean_rstd + (static_cast<long long>(b) * (nq * 4) + c) * 2 + 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[k].x = (v[k].x - s01.x) * s01.y;
+      v[k].y = (v[k].y - s01.z) * s01.w;
+      v[k].z = (v[k].z - s23.x) * s23.y;
+      v[k].w = (v[k].w - s23.z) * s23.w;
+    }
+  }
+  if (relu) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[k].x = fmaxf(v[k].x, 0.f);
+      v[k].y = fmaxf(v[k].y, 0.f);
+      v[k].z = fmaxf(v[k].z, 0.f);
+      v[k].w = fmaxf(v[k].w, 0.f);
+    }
+  }
+  float4 r;
+  r.x = ly0 * (lx0 * v[0].x + lx1 * v[1].x) + ly1 * (lx0 * v[2].x + lx1 * v[3].x);
+  r.y = ly0 * (lx0 * v[0].y + lx1 * v[1].y) + ly1 * (lx0 * v[2].y + lx1 * v[3].y);
+  r.z = ly0 * (lx0 * v[0].z + lx1 * v[1].z) + ly1 * (lx0 * v[2].z + lx1 * v[3].z);
+  r.w = ly0 * (lx0 * v[0].w + lx1 * v[1].w) + ly1 * (lx0 * v[2].w + lx1 * v[3].w);
+  *reinterpret_cast<float4*>(dst + static_cast<long long>(m) * dcs + dco + c) = r;
+}
+
+// 1x1 convolution C_in (<= 256) -> C_out (<= 32) + bias with an optional instance norm / ReLU on load, written NCHW, with the
+// epilogue linear / L2 normalisation over the outputs (F.normalize: x / max(|x|_2, 1e-12)) / sigmoid.  Workgroup = 4 waves
+// over a tile of 64 pixels; wave g owns outputs 8g..8g+7 of every pixel (lane = pixel).  The weights stay in LDS for all tiles
+// a workgroup walks; the activations pass through LDS in 64-channel chunks (coalesced 256-byte row reads), each read once.
+constexpr int PH_PIX = 64, PH_CH = 64, PH_CIN = 256, PH_COUT = 32;
+
+__global__ __launch_bounds__(256) void pixel_head_nhwc_kernel(const float* __restrict__ src, int scs, int sco, int c_in,
+                                                              const float* __restrict__ mean_rstd, int relu,
+                                                              const float* __restrict__ wgt, const float* __restrict__ bias,
+                                                              int c_out, int mode, float* __restrict__ dst, int HW, int npix) {
+  __shared__ float w_s[PH_CIN * PH_COUT];                   // [c][o], zero beyond c_in / c_out
+  __shared__ float x_s[PH_PIX * (PH_CH + 1)];               // [pixel][channel of the chunk], padded row
+  __shared__ float ss_s[4 * PH_PIX];                        // per-wave partial sums of squares (L2 mode)
+  const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;
+  for (int e = tid; e < PH_CIN * PH_COUT; e += 256) {
+    const int c = e / PH_COUT, o = e % PH_COUT;
+    w_s[e] = (c < c_in && o < c_out) ? wgt[o * c_in + c] : 0.f;
+  }
+  const bool active = g * 8 < c_out;                       // (wave-uniform)
+  float bo[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bo[j] = (g * 8 + j < c_out) ? bias[g * 8 + j] : 0.f;
+  __syncthreads();
+  const int ntiles = (npix + PH_PIX - 1) / PH_PIX;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int n0 = tile * PH_PIX;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = bo[j];
+    for (int c0 = 0; c0 < c_in; c0 += PH_CH) {
+      __syncthreads();                                     // (previous chunk consumed)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i, p = e >> 4, c = c0 + 4 * (e & 15);
+        const int n = n0 + p;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n < npix && c < c_in) {
+          v = *reinterpret_cast<const float4*>(src + static_cast<long long>(n) * scs + sco + c);
+          if (mean_rstd) {
+            const float* ms = mean_rstd + (static_cast<long long>(n / HW) * c_in + c) * 2;
+            v.x = (v.x - ms[0]) * ms[1];
+            v.y = (v.y - ms[2]) * ms[3];
+            v.z = (v.z - ms[4]) * ms[5];
+            v.w = (v.w - ms[6]) * ms[7];
+          }
+          if (relu) {
+            v.x = fmaxf(v.x, 0.f);
+            v.y = fmaxf(v.y, 0.f);
+            v.z = fmaxf(v.z, 0.f);
+            v.w = fmaxf(v.w, 0.f);
+          }
+        }
+        float* xp = x_s + p * (PH_CH + 1) + 4 * (e & 15);
+        xp[0] = v.x;
+        xp[1] = v.y;
+        xp[2] = v.z;
+        xp[3] = v.w;
+      }
+      __syncthreads();
+      if (active) {
+        const int cn = c_in - c0 < PH_CH ? c_in - c0 : PH_CH;
+        const float* xr = x_s + lane * (PH_CH + 1);
+        for (int c = 0; c < cn; ++c) {
+          const float x = xr[c];
+          const float4 wa = *reinterpret_cast<const float4*>(w_s + (c0 + c) * PH_COUT + g * 8);
+          const float4 wb = *reinterpret_cast<const float4*>(w_s + (c0 + c) * PH_COUT + g * 8 + 4);
+          acc[0] = fmaf(x, wa.x, acc[0]);
+          acc[1] = fmaf(x, wa.y, acc[1]);
+          acc[2] = fmaf(x, wa.z, acc[2]);
+          acc[3] = fmaf(x, wa.w, acc[3]);
+          acc[4] = fmaf(x, wb.x, acc[4]);
+          acc[5] = fmaf(x, wb.y, acc[5]);
+          acc[6] = fmaf(x, wb.z, acc[6]);
+          acc[7] = fmaf(x, wb.w, acc[7]);
+        }
+      }
+    }
+    float scale = 1.f;
+    if (mode == 1) {                                      // L2 over all c_out outputs of the pixel (outputs >= c_out are 0)
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss = fmaf(acc[j], acc[j], ss);
+      ss_s[g * PH_PIX + lane] = active ? ss : 0.f;
+      __syncthreads();
+      const float tot = (ss_s[lane] + ss_s[PH_PIX + lane]) + (ss_s[2 * PH_PIX + lane] + ss_s[3 * PH_PIX + lane]);
+      scale = 1.f / fmaxf(sqrtf(tot), 1e-12f);
+    }
+    const int n = n0 + lane;
+    if (active && n < npix) {
+      const int b = n / HW, pix = n - b * HW;
+      float* o = dst + (static_cast<long long>(b) * c_out + g * 8) * HW + pix;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (g * 8 + j >= c_out) break;
+        float y = acc[j];
+        if (mode == 1) y = acc[j] * scale;
+        else if (mode == 2) y = 1.f / (1.f + expf(-y));
+        o[static_cast<long long>(j) * HW] = y;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -722,6 +907,61 @@ int rnnpose_split_hl_f32(const float* src, int src_c_stride, int src_c_offset, l
   const long long total = n_pixels * (c_count / 8);
   hipLaunchKernelGGL(split_hl_kernel, dim3(rp::cdiv(total, 256)), dim3(256), 0, rp::as_stream(stream), src, src_c_stride, src_c_offset,
                      dst, dst_c_stride, dst_c_offset, c_count / 8, total, a_scale, rp::sat_counter());
+  return rp::check_launch(fn);
+}
+
+// ---- SuperPoint2D glue ------------------------------------------------------------------------------------------------
+static bool quad_window(const float* p, int c_stride, int c_offset, int c) {
+  return c > 0 && c % 4 == 0 && c_offset >= 0 && c_offset % 4 == 0 && c_stride % 4 == 0 && c_offset + c <= c_stride &&
+         reinterpret_cast<uintptr_t>(p) % 16 == 0;
+}
+
+int rnnpose_maxpool2x2_nhwc_f32(const float* src, int B, int H, int W, int src_c_stride, int src_c_offset, int C, float* dst,
+                                int dst_c_stride, int dst_c_offset, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_maxpool2x2_nhwc_f32";
+  RP_REQUIRE(src && dst, fn, "null pointer");
+  RP_REQUIRE(B > 0 && H >= 2 && W >= 2, fn, "bad size (H, W >= 2)");
+  RP_REQUIRE(static_cast<long long>(B) * H * W < (1LL << 31), fn, "B * H * W must be below 2^31");
+  RP_REQUIRE(quad_window(src, src_c_stride, src_c_offset, C) && quad_window(dst, dst_c_stride, dst_c_offset, C), fn,
+             "channel windows: C, offsets and strides multiples of 4, inside the stride, 16-byte aligned tensors");
+  const int Ho = H / 2, Wo = W / 2;
+  const long long total = static_cast<long long>(B) * Ho * Wo * (C / 4);
+  hipLaunchKernelGGL(maxpool2x2_nhwc_kernel, dim3(rp::cdiv(total, 256)), dim3(256), 0, rp::as_stream(stream), src, src_c_stride,
+                     src_c_offset, dst, dst_c_stride, dst_c_offset, H, W, Ho, Wo, C / 4, total);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_upsample2x_bilinear_nhwc_f32(const float* src, int B, int h, int w, int src_c_stride, int src_c_offset, int C,
+                                         const float* mean_rstd, int relu, float* dst, int dst_c_stride, int dst_c_offset,
+                                         rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_upsample2x_bilinear_nhwc_f32";
+  RP_REQUIRE(src && dst, fn, "null pointer");
+  RP_REQUIRE(B > 0 && h > 0 && w > 0, fn, "bad size");
+  RP_REQUIRE(static_cast<long long>(B) * h * w * 4 < (1LL << 31), fn, "B * 2h * 2w must be below 2^31");
+  RP_REQUIRE(quad_window(src, src_c_stride, src_c_offset, C) && quad_window(dst, dst_c_stride, dst_c_offset, C), fn,
+             "channel windows: C, offsets and strides multiples of 4, inside the stride, 16-byte aligned tensors");
+  RP_REQUIRE(!mean_rstd || reinterpret_cast<uintptr_t>(mean_rstd) % 16 == 0, fn, "mean_rstd must be 16-byte aligned");
+  const long long total = static_cast<long long>(B) * (2 * h) * (2 * w) * (C / 4);
+  hipLaunchKernelGGL(upsample2x_bilinear_nhwc_kernel, dim3(rp::cdiv(total, 256)), dim3(256), 0, rp::as_stream(stream), src,
+                     src_c_stride, src_c_offset, mean_rstd, relu, dst, dst_c_stride, dst_c_offset, h, w, C / 4, total);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_pixel_head_nhwc_f32(const float* src, int B, int HW, int src_c_stride, int src_c_offset, int c_in,
+                                const float* mean_rstd, int relu, const float* weight, const float* bias, int c_out, int mode,
+                                float* dst_nchw, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_pixel_head_nhwc_f32";
+  RP_REQUIRE(src && weight && bias && dst_nchw, fn, "null pointer");
+  RP_REQUIRE(B > 0 && HW > 0 && static_cast<long long>(B) * HW < (1LL << 31), fn, "bad size (B * HW below 2^31)");
+  RP_REQUIRE(c_in <= PH_CIN && quad_window(src, src_c_stride, src_c_offset, c_in), fn,
+             "c_in <= 256; channel window: c_in, offset and stride multiples of 4, inside the stride, 16-byte aligned");
+  RP_REQUIRE(c_out > 0 && c_out <= PH_COUT, fn, "c_out must be in 1..32");
+  RP_REQUIRE(mode >= 0 && mode <= 2, fn, "mode: 0 linear, 1 L2 normalise, 2 sigmoid");
+  const int npix = B * HW;
+  const int tiles = rp::cdiv(npix, PH_PIX);
+  const int cap = 3 * rp::cu_count();                     // (3 resident per CU by LDS) the weights are loaded once per workgroup: it walks several tiles
+  hipLaunchKernelGGL(pixel_head_nhwc_kernel, dim3(tiles < cap ? tiles : cap), dim3(256), 0, rp::as_stream(stream), src, src_c_stride,
+                     src_c_offset, c_in, mean_rstd, relu, weight, bias, c_out, mode, dst_nchw, HW, npix);
   return rp::check_launch(fn);
 }
 

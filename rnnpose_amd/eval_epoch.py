@@ -49,7 +49,7 @@ class EvalItem:
     K: np.ndarray                # (3,3)
     pose_init: np.ndarray        # (4,4) initial pose (PoseCNN / PVNet in the reference)
     pose_gt: np.ndarray          # (4,4)
-    geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image
+    geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image (None: HipEpoch(desc2d=...) computes them)
 
 
 class PackedEpochMetrics:
@@ -117,7 +117,7 @@ def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8
 class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
-    def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue")):
+    def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None):
         from .evaluator import LineMODEvaluator
         from .pose_refiner import PoseRefiner, default_config
         from .rasterizer import MeshRenderer
@@ -128,6 +128,9 @@ class HipEpoch:
         self.cfg = cfg if cfg is not None else default_config()
         self.refiner = refiner if refiner is not None else PoseRefiner(self.cfg, renderer=self.renderer).to(self.device).eval()
         self.symmetric = tuple(symmetric)
+        # desc2d: a descriptor2d.SuperPoint2D -- items without geofea_2d get theirs from the batch image on the device, as
+        # model/RNNPose.py:162 computes them (HybridNet.py:97 keeps the descriptors only)
+        self.desc2d = desc2d
         self.evaluators = {n: LineMODEvaluator(n, m.eval_points if m.eval_points is not None else m.verts, m.diameter,
                                                device=device) for n, m in models.items()}
         for n, e in self.evaluators.items():
@@ -137,7 +140,19 @@ class HipEpoch:
         from .transformation import SE3Sequence
         dev, m = self.device, self.models[cls]
         image = torch.stack([it.image for it in batch]).to(dev)
-        g2 = torch.stack([it.geofea_2d for it in batch]).to(dev)
+        missing = [j for j, it in enumerate(batch) if it.geofea_2d is None]
+        if missing and self.desc2d is None:
+            raise ValueError("items without geofea_2d need HipEpoch(desc2d=SuperPoint2D(...))")
+        if missing:
+            fresh = self.desc2d.descriptors(image.float() if len(missing) == len(batch) else image[missing].float())
+            if len(missing) == len(batch):
+                g2 = fresh
+            else:
+                given = iter(it.geofea_2d for it in batch if it.geofea_2d is not None)
+                got = iter(fresh)
+                g2 = torch.stack([next(got) if it.geofea_2d is None else next(given).to(dev) for it in batch])
+        else:
+            g2 = torch.stack([it.geofea_2d for it in batch]).to(dev)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
         T0 = torch.as_tensor(np.stack([it.pose_init for it in batch]).astype(np.float32)).to(dev)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)

@@ -1145,6 +1145,91 @@ def instnorm_tiles_nhwc(x, tile_stats, relu=True, residual=None, out=None, eps: 
     return out
 
 
+# ---- SuperPoint2D glue (model/descriptor2D.py; rnnpose_amd/descriptor2d.py) --------------------------------------------
+def _window(t, c_offset, c_count, name):
+    _nhwc(t, name)
+    Cs = t.shape[3]
+    c_count = Cs - c_offset if c_count is None else int(c_count)
+    if not (c_count > 0 and c_offset >= 0 and c_offset + c_count <= Cs):
+        raise ValueError(f"{name}: channel window [{c_offset}, {c_offset}+{c_count}) outside its {Cs} channels")
+    return c_count
+
+
+def _mean_rstd(mr, B, Cc):
+    if mr is None:
+        return None
+    if not (mr.is_cuda and mr.dtype == F32 and mr.is_contiguous() and tuple(mr.shape) == (B, Cc, 2)):
+        raise ValueError(f"mean_rstd must be a contiguous fp32 CUDA tensor of (B, C, 2) = ({B}, {Cc}, 2)")
+    return mr
+
+
+def maxpool2x2_nhwc(src, dst=None, src_c_offset: int = 0, c_count: int | None = None, dst_c_offset: int = 0):
+    """nn.MaxPool2d(2, 2) (floor) of channels [src_c_offset, +c_count) of src (B,H,W,Cs) -> channels [dst_c_offset, +c_count) of
+    dst (B,H//2,W//2,Cd) (allocated (B,H//2,W//2,c_count) if None)."""
+    c_count = _window(src, src_c_offset, c_count, "src")
+    B, H, W, _ = src.shape
+    if dst is None:
+        dst = torch.empty(B, H // 2, W // 2, c_count, device=src.device, dtype=F32)
+    _window(dst, dst_c_offset, c_count, "dst")
+    if tuple(dst.shape[:3]) != (B, H // 2, W // 2):
+        raise ValueError("dst must be (B, H//2, W//2, C)")
+    n_out = B * (H // 2) * (W // 2) * c_count
+    _launch("rnnpose_maxpool2x2_nhwc_f32", _ptr(src), B, H, W, src.shape[3], src_c_offset, c_count, _ptr(dst), dst.shape[3],
+            dst_c_offset, _stream(), work=3.0 * n_out, nbytes=4.0 * 5 * n_out)
+    return dst
+
+
+def upsample2x_nhwc(src, dst=None, src_c_offset: int = 0, c_count: int | None = None, dst_c_offset: int = 0, mean_rstd=None,
+                    relu: bool = False):
+    """nn.Upsample(scale_factor=2, mode='bilinear') (align_corners=False) of channels [src_c_offset, +c_count) of src (B,h,w,Cs)
+    -> channels [dst_c_offset, +c_count) of dst (B,2h,2w,Cd) (allocated (B,2h,2w,c_count) if None).
+    mean_rstd (B, c_count, 2) (instnorm_tiles_nhwc(..., stats_only=True) of the window): taps are read as (x - mean) * rstd
+    [then ReLU]: up(relu(IN(x))) without materialising the norm.  Per channel, so up(cat(a, b)) = cat(up(a), up(b))."""
+    c_count = _window(src, src_c_offset, c_count, "src")
+    B, h, w, _ = src.shape
+    if dst is None:
+        dst = torch.empty(B, 2 * h, 2 * w, c_count, device=src.device, dtype=F32)
+    _window(dst, dst_c_offset, c_count, "dst")
+    if tuple(dst.shape[:3]) != (B, 2 * h, 2 * w):
+        raise ValueError("dst must be (B, 2h, 2w, C)")
+    mr = _mean_rstd(mean_rstd, B, c_count)
+    n_out = B * 4 * h * w * c_count
+    _launch("rnnpose_upsample2x_bilinear_nhwc_f32", _ptr(src), B, h, w, src.shape[3], src_c_offset, c_count, _ptr(mr), int(bool(relu)),
+            _ptr(dst), dst.shape[3], dst_c_offset, _stream(), work=(6.0 + 12.0 * (mr is not None)) * n_out,
+            nbytes=4.0 * (n_out + B * h * w * c_count))
+    return dst
+
+
+PH_LINEAR, PH_L2, PH_SIGMOID = 0, 1, 2
+
+
+def pixel_head_nhwc(src, weight, bias, mode: int = PH_LINEAR, src_c_offset: int = 0, c_in: int | None = None, mean_rstd=None,
+                    relu: bool = False, out=None):
+    """1x1 convolution of channels [src_c_offset, +c_in) of src (B,H,W,Cs) (c_in <= 256) with weight (c_out, c_in[,1,1]) (c_out
+    <= 32) + bias -> out (B,c_out,H,W) NCHW.  The source is read as relu?((x - mean) * rstd) with mean_rstd (B,c_in,2), relu(x)
+    with relu alone.  mode: PH_LINEAR, PH_L2 (F.normalize over the outputs, eps 1e-12), PH_SIGMOID."""
+    c_in = _window(src, src_c_offset, c_in, "src")
+    B, H, W, _ = src.shape
+    w = _chk(weight.detach(), "weight")
+    w = w.reshape(w.shape[0], -1)
+    b = _chk(bias.detach(), "bias")
+    c_out = w.shape[0]
+    if w.shape[1] != c_in or tuple(b.shape) != (c_out,):
+        raise ValueError(f"weight must be (c_out, {c_in}) and bias (c_out,)")
+    if int(mode) not in (PH_LINEAR, PH_L2, PH_SIGMOID):
+        raise ValueError("mode must be PH_LINEAR, PH_L2 or PH_SIGMOID")
+    mr = _mean_rstd(mean_rstd, B, c_in)
+    if out is None:
+        out = torch.empty(B, c_out, H, W, device=src.device, dtype=F32)
+    if not (out.is_cuda and out.dtype == F32 and out.is_contiguous() and tuple(out.shape) == (B, c_out, H, W)):
+        raise ValueError(f"out must be a contiguous fp32 CUDA tensor of ({B}, {c_out}, {H}, {W})")
+    npx = B * H * W
+    _launch("rnnpose_pixel_head_nhwc_f32", _ptr(src), B, H * W, src.shape[3], src_c_offset, c_in, _ptr(mr), int(bool(relu)), _ptr(w),
+            _ptr(b), c_out, int(mode), _ptr(out), _stream(), work=2.0 * npx * c_in * c_out,
+            nbytes=4.0 * (npx * (c_in + c_out) + c_out * (c_in + 1)))
+    return out
+
+
 # ---- f2/f3: evaluator metrics ------------------------------------------------------------------------------------
 def nn_search(ref_pts, que_pts, exclude_self: bool = False):
     """ref (B,N1,D), que (B,N2,D) fp32 on the GPU, D in {2,3} -> idx (B,N2) int32: first nearest reference point."""
