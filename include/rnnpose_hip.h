@@ -435,6 +435,55 @@ int rnnpose_upsample2x_bilinear_nhwc_f32(const float* src, int B, int h, int w, 
 int rnnpose_pixel_head_nhwc_f32(const float* src, int B, int HW, int src_c_stride, int src_c_offset, int c_in,
                                 const float* mean_rstd, int relu, const float* weight, const float* bias, int c_out, int mode,
                                 float* dst_nchw, rnnpose_stream_t stream);
+/* ---- KPSuperpoint3Dv2 (model/descriptor3D.py on thirdparty/kpconv/kpconv_blocks.py; rnnpose_amd/descriptor3d.py) -----------
+ * Rows are points: a feature matrix is (N, C) fp32 with row stride ld >= C (a channel slice of a wider buffer is passed as its
+ * first element's address and the buffer's stride).  Neighbour tables are int32 (n_q, width); the value n_s (the support's
+ * row count over all stacked clouds) is the shadow neighbour; rows beyond 2^31 elements use 64-bit offsets.
+ * point_row_sum: out[i] = sum_c x[i, c] (the positive-sum neighbour count, kpconv_blocks.py:366-369).
+ * kpconv_aggregate: KPConv.forward (:300-372; linear influence, sum aggregation, rigid kernel) up to its weight product:
+ *   wf (n_q, K * c_in) contiguous, column k * c_in + c = sum_j clamp(1 - |s_j - q - kp_k| / extent, 0) x[j, c] / max(1, #{j real:
+ *   row_sum[j] > 0}); neighbours = neighbors[q, :width] (indices in 0..n_s), kernel_points (K, 3), K <= 16, c_in <= 256.
+ *   rnnpose_point_linear_f32(wf, .., K * c_in, weights (K, c_in, c_out) as (K c_in, c_out)) finishes the convolution.
+ * point_linear: out[i, j] = sum_k a[i, k] w[k, j] (+ bias[j] if bias), w (k, m) contiguous; fp32 FMA in k order (:505, :524,
+ *   model/descriptor3D.py:91-93 bottle / proj_gnn).
+ * point_norm_stats: InstanceNorm1d over ALL n rows (:456-473, no affine, biased variance): mean_rstd (c, 2) = (mean, 1/sqrt(var + eps)),
+ *   fp64 accumulation; workspace of rnnpose_point_norm_workspace_bytes(n, c).
+ * point_norm_apply: out = (x - mean) * rstd [+ res, read as (res - mean_r) * rstd_r when res_mean_rstd] [then LeakyReLU(slope) when
+ *   leaky]: UnaryBlock / SimpleBlock / the ResnetBottleneckBlock tail (:514-519, :585, :659-687).  out may be x.
+ * point_maxpool: max_pool (:88-104): out[q, c] = max_j x[idx[q, j], c] with the shadow row = 0.
+ * point_gather_rows: closest_pool (:73-85): out[q, c] = x[idx[q * idx_ld], c], 0 for the shadow.
+ * point_l2_normalize: F.normalize(p=2, dim=1, eps=1e-12) of each row (model/descriptor3D.py:134-136); out may be x.
+ * grid_voxel_keys: grid_subsampling.cpp:50-56 for one cloud: keys[i] = ix + nx iy + nx ny iz with ix = floor((p.x - ox) / dl) in fp32
+ *   (correctly rounded division), likewise iy, iz.
+ * radius_count / radius_neighbors: batch_query (cpp_neighbors/neighbors/neighbors.cpp:229-330).  Clouds b = 0..n_clouds-1 are
+ *   query rows [q_start[b], q_start[b+1]) and support rows [s_start[b], s_start[b+1]) (device int32, n_clouds + 1 entries);
+ *   support j is a neighbour of q when ((dx^2 + dy^2) + dz^2) < radius^2 in fp32.  count: counts[q].  neighbors: offsets[q]
+ *   (int64) = exclusive prefix sum of counts, cand_idx / cand_d2 of sum(counts) entries (scratch), out (n_q, width) PRE-FILLED
+ *   with the shadow index: the neighbours sorted by (d2, index), the first width of them. */
+int rnnpose_point_row_sum_f32(const float* x, int n, int c, long long ldx, float* out, rnnpose_stream_t stream);
+int rnnpose_kpconv_aggregate_f32(const float* q_pts, int n_q, const float* s_pts, int n_s, const int* neighbors, int width,
+                                 const float* kernel_points, int K, float extent, const float* x, int c_in, long long ldx,
+                                 const float* row_sum, float* wf, rnnpose_stream_t stream);
+int rnnpose_point_linear_f32(const float* a, int n, int k, long long lda, const float* w, int m, const float* bias, float* out,
+                             long long ldo, rnnpose_stream_t stream);
+long long rnnpose_point_norm_workspace_bytes(int n, int c);
+int rnnpose_point_norm_stats_f32(const float* x, int n, int c, long long ldx, float eps, void* workspace, long long workspace_bytes,
+                                 float* mean_rstd, rnnpose_stream_t stream);
+int rnnpose_point_norm_apply_f32(const float* x, int n, int c, long long ldx, const float* mean_rstd, const float* res, long long ldr,
+                                 const float* res_mean_rstd, int leaky, float slope, float* out, long long ldo,
+                                 rnnpose_stream_t stream);
+int rnnpose_point_maxpool_f32(const float* x, int n_s, int c, long long ldx, const int* idx, int n_q, int width, float* out,
+                              long long ldo, rnnpose_stream_t stream);
+int rnnpose_point_gather_rows_f32(const float* x, int n_s, int c, long long ldx, const int* idx, int n_q, int idx_ld, float* out,
+                                  long long ldo, rnnpose_stream_t stream);
+int rnnpose_point_l2_normalize_f32(const float* x, int n, int c, long long ldx, float* out, long long ldo, rnnpose_stream_t stream);
+int rnnpose_grid_voxel_keys_f32(const float* points, int n, float ox, float oy, float oz, float dl, long long nx, long long ny,
+                                long long* keys, rnnpose_stream_t stream);
+int rnnpose_radius_count_f32(const float* queries, int n_q, const float* supports, const int* q_start, const int* s_start,
+                             int n_clouds, float radius, int* counts, rnnpose_stream_t stream);
+int rnnpose_radius_neighbors_f32(const float* queries, int n_q, const float* supports, const int* q_start, const int* s_start,
+                                 int n_clouds, float radius, const long long* offsets, int* cand_idx, float* cand_d2, int width,
+                                 int* out, rnnpose_stream_t stream);
 /* 1x1 convolution (+ bias, optional ReLU) with the activation tile resident in LDS: 32 pixels x ALL 256 output columns per
  * workgroup, the tile split into fp16 hi / lo once (the implicit-GEMM kernel re-splits it per 64-column tile).  Used for
  * BasicMotionEncoder.convc1 (thirdparty/raft/update.py:80,87: 324 -> 256).  pack: weight (256, c_in) fp32 -> MFMA fragments

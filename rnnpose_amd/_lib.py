@@ -106,6 +106,18 @@ PROTOTYPES = {
     "rnnpose_maxpool2x2_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p]),
     "rnnpose_upsample2x_bilinear_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
     "rnnpose_pixel_head_nhwc_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p]),
+    "rnnpose_point_row_sum_f32": (_i, [_p, _i, _i, _ll, _p, _p]),
+    "rnnpose_kpconv_aggregate_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _f, _p, _i, _ll, _p, _p, _p]),
+    "rnnpose_point_linear_f32": (_i, [_p, _i, _i, _ll, _p, _i, _p, _p, _ll, _p]),
+    "rnnpose_point_norm_workspace_bytes": (_ll, [_i, _i]),
+    "rnnpose_point_norm_stats_f32": (_i, [_p, _i, _i, _ll, _f, _p, _ll, _p, _p]),
+    "rnnpose_point_norm_apply_f32": (_i, [_p, _i, _i, _ll, _p, _p, _ll, _p, _i, _f, _p, _ll, _p]),
+    "rnnpose_point_maxpool_f32": (_i, [_p, _i, _i, _ll, _p, _i, _i, _p, _ll, _p]),
+    "rnnpose_point_gather_rows_f32": (_i, [_p, _i, _i, _ll, _p, _i, _i, _p, _ll, _p]),
+    "rnnpose_point_l2_normalize_f32": (_i, [_p, _i, _i, _ll, _p, _ll, _p]),
+    "rnnpose_grid_voxel_keys_f32": (_i, [_p, _i, _f, _f, _f, _f, _ll, _ll, _p, _p]),
+    "rnnpose_radius_count_f32": (_i, [_p, _i, _p, _p, _p, _i, _f, _p, _p]),
+    "rnnpose_radius_neighbors_f32": (_i, [_p, _i, _p, _p, _p, _i, _f, _p, _p, _p, _i, _p, _p]),
     "rnnpose_flow_head_out_f32": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "rnnpose_convex_upsample_nhwc_f32": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "rnnpose_mask_upsample_f16x3": (_i, [_p, _i, _i, _p, _i, _p, _f, _f, _p, _i, _i, _i, _p, _p]),

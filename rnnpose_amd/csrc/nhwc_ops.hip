@@ -966,3 +966,538 @@ int rnnpose_pixel_head_nhwc_f32(const float* src, int B, int HW, int src_c_strid
 }
 
 }  // extern "C"
+
+// ==== KPSuperpoint3Dv2 ====================================================================================================
+// KPSuperpoint3Dv2 (model/descriptor3D.py on thirdparty/kpconv/kpconv_blocks.py) and the radius search of its input pyramid
+// (thirdparty/kpconv/cpp_wrappers/cpp_neighbors/neighbors/neighbors.cpp:229-330): rnnpose_amd/descriptor3d.py.
+// Rows are points.  A feature matrix is (N, C) fp32 with a row stride ld >= C, so that a block reads or writes a channel slice
+// of a wider buffer (the decoder's concat buffers).  Neighbour tables are int32 (n_q, width); the value n_s (the row count of
+// the support, all stacked clouds) is the shadow neighbour.  Every multiply-add is fp32; no atomics: every launch is
+// deterministic, and each output's summation order does not depend on the launch shape.  Where an operation order restates the
+// reference, contraction is off (#pragma clang fp contract(off)); fp32 division and square root are correctly rounded (hipcc's default).
+
+namespace {
+
+using i64 = long long;
+constexpr int KP_MAX = 16;       // kernel points per KPConv (the shipped configuration: 15)
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// ---- per-row feature sums: the positive-sum neighbour count of KPConv (kpconv_blocks.py:366-369) -----------------------
+__global__ __launch_bounds__(256) void row_sum_kernel(const float* __restrict__ x, int n, int c, i64 ldx, float* __restrict__ out) {
+  const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (row >= n) return;                 // whole waves
+  const float* r = x + row * ldx;
+  float s = 0.f;
+  for (int k = lane; k < c; k += 64) s += r[k];
+  s = wave_sum(s);
+  if (lane == 0) out[row] = s;
+}
+
+// ---- KPConv aggregation (kpconv_blocks.py:300-372, KP_influence 'linear', aggregation 'sum', not deformable) -------------
+// One wave per query point, four per workgroup.  Per chunk of 64 neighbours, lane j computes neighbour j's K influences in the
+// reference's order -- n = s - q; d = n - kp; d2 = (dx^2 + dy^2) + dz^2; clamp(1 - sqrt(d2) / extent, 0) -- into LDS; then
+// every lane accumulates its channels: WF[k, c] += infl[j, k] * x[j, c] (fp32 FMA, neighbours in table order).  The shadow
+// neighbour (a point at 1e6 with a zero row) adds exactly nothing and is skipped.  The divisor is max(1, #{j : row_sum[j] > 0})
+// over the REAL neighbours (the shadow row sums to 0).  Out: wf (n_q, K * c_in), column k * c_in + c = WF[k, c] / count: the
+// operand of the (15 c_in) x c_out product, whose weight is KPConv.weights (K, c_in, c_out) read as (K c_in, c_out).
+template <int CPL>
+__global__ __launch_bounds__(256) void kpconv_aggregate_kernel(const float* __restrict__ q_pts, const float* __restrict__ s_pts, int n_q,
+                                                               int n_s, const int* __restrict__ nb, int width,
+                                                               const float* __restrict__ kp, int K, float extent,
+                                                               const float* __restrict__ x, int c_in, i64 ldx,
+                                                               const float* __restrict__ row_sum, float* __restrict__ wf) {
+#pragma clang fp contract(off)
+  __shared__ float s_inf[4][64][KP_MAX];
+  __shared__ int s_idx[4][64];
+  __shared__ float s_kp[KP_MAX * 3];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + w;
+  const bool active = q < n_q;
+  if (threadIdx.x < K * 3) s_kp[threadIdx.x] = kp[threadIdx.x];
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) {
+    qx = q_pts[3 * static_cast<i64>(q)];
+    qy = q_pts[3 * static_cast<i64>(q) + 1];
+    qz = q_pts[3 * static_cast<i64>(q) + 2];
+  }
+  float acc[CPL][KP_MAX];
+#pragma unroll
+  for (int cc = 0; cc < CPL; ++cc)
+#pragma unroll
+    for (int k = 0; k < KP_MAX; ++k) acc[cc][k] = 0.f;
+  int cnt = 0;
+  const int* row = nb + static_cast<i64>(active ? q : 0) * width;
+  __syncthreads();
+  for (int j0 = 0; j0 < width; j0 += 64) {
+    const int nj = min(64, width - j0);
+    if (active && lane < nj) {
+      const int id = row[j0 + lane];
+      const bool real = id >= 0 && id < n_s;
+      s_idx[w][lane] = real ? id : -1;
+      if (real) {
+        cnt += row_sum[id] > 0.f;
+        const float nx = s_pts[3 * static_cast<i64>(id)] - qx;
+        const float ny = s_pts[3 * static_cast<i64>(id) + 1] - qy;
+        const float nz = s_pts[3 * static_cast<i64>(id) + 2] - qz;
+#pragma unroll
+        for (int k = 0; k < KP_MAX; ++k) {
+          if (k < K) {
+            const float dx = nx - s_kp[3 * k], dy = ny - s_kp[3 * k + 1], dz = nz - s_kp[3 * k + 2];
+            const float d2 = (dx * dx + dy * dy) + dz * dz;
+            s_inf[w][lane][k] = fmaxf(1.f - sqrtf(d2) / extent, 0.f);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int j = 0; j < nj; ++j) {
+        const int id = s_idx[w][j];
+        if (id < 0) continue;                                   // uniform across the wave
+        const float* xr = x + id * ldx;
+        float f[CPL];
+#pragma unroll
+        for (int cc = 0; cc < CPL; ++cc) {
+          const int c = lane + 64 * cc;
+          f[cc] = c < c_in ? xr[c] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < KP_MAX; ++k) {
+          if (k < K) {
+            const float a = s_inf[w][j][k];
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) acc[cc][k] = fmaf(a, f[cc], acc[cc][k]);
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  const float count = static_cast<float>(max(1, wave_sum_i(cnt)));
+  float* out = wf + static_cast<i64>(q) * K * c_in;
+#pragma unroll
+  for (int k = 0; k < KP_MAX; ++k) {
+    if (k < K) {
+#pragma unroll
+      for (int cc = 0; cc < CPL; ++cc) {
+        const int c = lane + 64 * cc;
+        if (c < c_in) out[k * c_in + c] = acc[cc][k] / count;
+      }
+    }
+  }
+}
+
+// ---- dense product: out[i, j] = sum_k a[i, k] w[k, j] (+ bias[j]) -------------------------------------------------------
+// BM x 64 tiles, K in steps of 16 through LDS, 256 threads with (BM / 16) x 4 outputs each.  Every output is ONE fp32 FMA chain
+// over k = 0, 1, ... (zero padding appends exact zeros), so the result does not depend on BM.  BM = 16 keeps coarse levels
+// (about a hundred points) on several workgroups per 64 output columns.
+template <int BM>
+__global__ __launch_bounds__(256) void point_linear_kernel(const float* __restrict__ a, i64 lda, int n, int kdim,
+                                                           const float* __restrict__ wt, int m, const float* __restrict__ bias,
+                                                           float* __restrict__ out, i64 ldo) {
+  constexpr int RM = BM / 16;
+  __shared__ float As[16][BM + 1];
+  __shared__ float Bs[16][64];
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int row0 = blockIdx.y * BM, col0 = blockIdx.x * 64;
+  float acc[RM][4];
+#pragma unroll
+  for (int i = 0; i < RM; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  for (int k0 = 0; k0 < kdim; k0 += 16) {
+    for (int e = t; e < BM * 16; e += 256) {
+      const int r = e >> 4, kk = e & 15, gr = row0 + r, gk = k0 + kk;
+      As[kk][r] = (gr < n && gk < kdim) ? a[gr * lda + gk] : 0.f;
+    }
+    for (int e = t; e < 16 * 64; e += 256) {
+      const int kk = e >> 6, cc = e & 63, gk = k0 + kk, gc = col0 + cc;
+      Bs[kk][cc] = (gk < kdim && gc < m) ? wt[static_cast<i64>(gk) * m + gc] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) {
+      float av[RM], bv[4];
+#pragma unroll
+      for (int i = 0; i < RM; ++i) av[i] = As[kk][ty + 16 * i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bv[j] = Bs[kk][tx + 16 * j];
+#pragma unroll
+      for (int i = 0; i < RM; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < RM; ++i) {
+    const int r = row0 + ty + 16 * i;
+    if (r >= n) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = col0 + tx + 16 * j;
+      if (c < m) out[r * ldo + c] = bias ? acc[i][j] + bias[c] : acc[i][j];
+    }
+  }
+}
+
+// ---- instance norm over all rows (BatchNormBlock = InstanceNorm1d on (1, C, N), kpconv_blocks.py:456-473) -----------------
+// Pass 1: fp64 sum and sum of squares of each channel over a chunk of rows (64 channels x 4 row phases per workgroup).
+// Pass 2: chunks summed in order; mean, biased variance, rstd = 1 / sqrt(var + eps) in fp64, stored fp32 as (C, 2).
+constexpr int NORM_CHUNK_ROWS = 512;
+
+__global__ __launch_bounds__(256) void norm_partial_kernel(const float* __restrict__ x, i64 ldx, int n, int c, double* __restrict__ ws) {
+  __shared__ double sh[2][4][64];
+  const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
+  const int ch = blockIdx.x * 64 + lane, chunk = blockIdx.y;
+  const int r0 = chunk * NORM_CHUNK_ROWS, r1 = min(n, r0 + NORM_CHUNK_ROWS);
+  double s = 0.0, ss = 0.0;
+  if (ch < c)
+    for (int r = r0 + ph; r < r1; r += 4) {
+      const double v = x[r * ldx + ch];
+      s += v;
+      ss += v * v;
+    }
+  sh[0][ph][lane] = s;
+  sh[1][ph][lane] = ss;
+  __syncthreads();
+  if (ph == 0 && ch < c) {
+    double* o = ws + (static_cast<i64>(chunk) * c + ch) * 2;
+    o[0] = ((sh[0][0][lane] + sh[0][1][lane]) + sh[0][2][lane]) + sh[0][3][lane];
+    o[1] = ((sh[1][0][lane] + sh[1][1][lane]) + sh[1][2][lane]) + sh[1][3][lane];
+  }
+}
+
+__global__ __launch_bounds__(256) void norm_final_kernel(const double* __restrict__ ws, int chunks, int n, int c, float eps,
+                                                         float* __restrict__ mean_rstd) {
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= c) return;
+  double s = 0.0, ss = 0.0;
+  for (int k = 0; k < chunks; ++k) {
+    s += ws[(static_cast<i64>(k) * c + ch) * 2];
+    ss += ws[(static_cast<i64>(k) * c + ch) * 2 + 1];
+  }
+  const double mean = s / n;
+  const double var = fmax(ss / n - mean * mean, 0.0);
+  mean_rstd[2 * ch] = static_cast<float>(mean);
+  mean_rstd[2 * ch + 1] = static_cast<float>(1.0 / sqrt(var + static_cast<double>(eps)));
+}
+
+// y = (x - mean) * rstd, then + res (read as (res - mean_r) * rstd_r when res_mean_rstd is given), then LeakyReLU(slope)
+// when leaky: UnaryBlock (:514-519), SimpleBlock (:585) and the ResnetBottleneckBlock tail leaky(IN(unary2) + shortcut) (:686).
+__global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict__ x, i64 ldx, int n, int c,
+                                                         const float* __restrict__ mr, const float* __restrict__ res, i64 ldr,
+                                                         const float* __restrict__ mr_res, int leaky, float slope,
+                                                         float* __restrict__ out, i64 ldo) {
+#pragma clang fp contract(off)
+  const i64 e = static_cast<i64>(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= static_cast<i64>(n) * c) return;
+  const i64 r = e / c;
+  const int ch = static_cast<int>(e - r * c);
+  float y = (x[r * ldx + ch] - mr[2 * ch]) * mr[2 * ch + 1];
+  if (res) {
+    float s = res[r * ldr + ch];
+    if (mr_res) s = (s - mr_res[2 * ch]) * mr_res[2 * ch + 1];
+    y = y + s;
+  }
+  if (leaky && !(y > 0.f)) y = y * slope;
+  out[r * ldo + ch] = y;
+}
+
+// ---- max_pool (:88-104): max over the neighbour rows, the shadow row being zeros ---------------------------------------------
+__global__ __launch_bounds__(256) void point_maxpool_kernel(const float* __restrict__ x, i64 ldx, int n_s, int c,
+                                                            const int* __restrict__ idx, int n_q, int width, float* __restrict__ out,
+                                                            i64 ldo) {
+  const i64 e = static_cast<i64>(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= static_cast<i64>(n_q) * c) return;
+  const i64 q = e / c;
+  const int ch = static_cast<int>(e - q * c);
+  const int* row = idx + q * width;
+  float m = 0.f;
+  for (int j = 0; j < width; ++j) {
+    const int id = row[j];
+    const float v = (id >= 0 && id < n_s) ? x[id * ldx + ch] : 0.f;
+    m = j == 0 ? v : fmaxf(m, v);
+  }
+  out[q * ldo + ch] = m;
+}
+
+// ---- closest_pool (:73-85): row idx[q, 0], zeros for the shadow ---------------------------------------------------------------
+__global__ __launch_bounds__(256) void point_gather_kernel(const float* __restrict__ x, i64 ldx, int n_s, int c,
+                                                           const int* __restrict__ idx, int idx_ld, int n_q, float* __restrict__ out,
+                                                           i64 ldo) {
+  const i64 e = static_cast<i64>(blockIdx.x) * 256 + threadIdx.x;
+  if (e >= static_cast<i64>(n_q) * c) return;
+  const i64 q = e / c;
+  const int ch = static_cast<int>(e - q * c);
+  const int id = idx[q * idx_ld];
+  out[q * ldo + ch] = (id >= 0 && id < n_s) ? x[id * ldx + ch] : 0.f;
+}
+
+// ---- radius search (neighbors.cpp:229-330) -------------------------------------------------------------------------------------
+// Query q of cloud b searches supports [s_start[b], s_start[b + 1]) only.  d2 = ((dx^2 + dy^2) + dz^2) in fp32 without
+// contraction, dx = q.x - s.x (nanoflann's L2_Simple_Adaptor); a support is a neighbour when d2 < r2, r2 = r * r in fp32.
+// Supports are staged through LDS 256 at a time over the union of the clouds of the workgroup's queries.
+__device__ __forceinline__ int cloud_of(const int* __restrict__ start, int B, int i) {
+  int b = 0;
+  while (b + 1 < B && i >= start[b + 1]) ++b;
+  return b;
+}
+
+__device__ __forceinline__ float sq_dist(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+  const float dx = ax - bx, dy = ay - by, dz = az - bz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// mode 0: counts[q] = number of neighbours.  mode 1: the neighbours (support order) into cand[offsets[q] ...], then each one's
+// rank by (d2, index) among them, and ranks < width written to out[q, rank] (out pre-filled with the shadow index).
+template <int MODE>
+__global__ __launch_bounds__(256) void radius_kernel(const float* __restrict__ qp, int n_q, const float* __restrict__ sp,
+                                                     const int* __restrict__ q_start, const int* __restrict__ s_start, int B,
+                                                     float radius, int* __restrict__ counts, const i64* __restrict__ offsets,
+                                                     int* __restrict__ cand_idx, float* __restrict__ cand_d2, int width,
+                                                     int* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ float ts[3][256];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int q_first = blockIdx.x * 256, q_last = min(n_q, q_first + 256) - 1;
+  const int b_lo = cloud_of(q_start, B, q_first), b_hi = cloud_of(q_start, B, q_last);
+  const int u0 = s_start[b_lo], u1 = s_start[b_hi + 1];
+  const bool active = q < n_q;
+  int s0 = 0, s1 = 0;
+  float x = 0.f, y = 0.f, z = 0.f;
+  if (active) {
+    const int b = cloud_of(q_start, B, q);
+    s0 = s_start[b];
+    s1 = s_start[b + 1];
+    x = qp[3 * static_cast<i64>(q)];
+    y = qp[3 * static_cast<i64>(q) + 1];
+    z = qp[3 * static_cast<i64>(q) + 2];
+  }
+  const float r2 = radius * radius;
+  int cnt = 0;
+  const i64 base = (MODE == 1 && active) ? offsets[q] : 0;
+  for (int t0 = u0; t0 < u1; t0 += 256) {
+    const int j = t0 + threadIdx.x;
+    if (j < u1) {
+      ts[0][threadIdx.x] = sp[3 * static_cast<i64>(j)];
+      ts[1][threadIdx.x] = sp[3 * static_cast<i64>(j) + 1];
+      ts[2][threadIdx.x] = sp[3 * static_cast<i64>(j) + 2];
+    }
+    __syncthreads();
+    const int lo = max(s0, t0), hi = min(s1, min(u1, t0 + 256));
+#pragma clang loop vectorize(disable)          // no packed fp32 in this library (rnnpose_amd/build.py, tests/test_isa_guard.py)
+    for (int jj = lo; jj < hi; ++jj) {
+      const int l = jj - t0;
+      const float d2 = sq_dist(x, y, z, ts[0][l], ts[1][l], ts[2][l]);
+      if (d2 < r2) {
+        if (MODE == 1) {
+          cand_idx[base + cnt] = jj;
+          cand_d2[base + cnt] = d2;
+        }
+        ++cnt;
+      }
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  if (MODE == 0) {
+    counts[q] = cnt;
+    return;
+  }
+  for (int a = 0; a < cnt; ++a) {
+    const float da = cand_d2[base + a];
+    const int ia = cand_idx[base + a];
+    int rank = 0;
+    for (int b = 0; b < cnt; ++b) {
+      const float db = cand_d2[base + b];
+      rank += (db < da) || (db == da && cand_idx[base + b] < ia);
+    }
+    if (rank < width) out[static_cast<i64>(q) * width + rank] = ia;
+  }
+}
+
+// ---- F.normalize(p=2, dim=1, eps=1e-12) of the output rows (model/descriptor3D.py:134-136): one wave per row --------------------
+__global__ __launch_bounds__(256) void l2_rows_kernel(const float* __restrict__ x, i64 ldx, int n, int c, float* __restrict__ out,
+                                                      i64 ldo) {
+  const int row = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+  if (row >= n) return;                 // whole waves
+  const float* r = x + row * ldx;
+  float s = 0.f;
+  for (int k = lane; k < c; k += 64) s = fmaf(r[k], r[k], s);
+  const float nrm = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+  for (int k = lane; k < c; k += 64) out[row * ldo + k] = r[k] / nrm;
+}
+
+// ---- voxel keys of grid subsampling (cpp_subsampling/grid_subsampling/grid_subsampling.cpp:50-56) -------------------------------
+// i = floor((p - origin) / dl) per axis, fp32 with a correctly rounded division; key = ix + nx iy + nx ny iz.
+__global__ __launch_bounds__(256) void grid_keys_kernel(const float* __restrict__ p, int n, float ox, float oy, float oz, float dl, i64 nx,
+                                                        i64 ny, i64* __restrict__ keys) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const i64 ix = static_cast<i64>(floorf((p[3 * static_cast<i64>(i)] - ox) / dl));
+  const i64 iy = static_cast<i64>(floorf((p[3 * static_cast<i64>(i) + 1] - oy) / dl));
+  const i64 iz = static_cast<i64>(floorf((p[3 * static_cast<i64>(i) + 2] - oz) / dl));
+  keys[i] = ix + nx * iy + nx * ny * iz;
+}
+
+bool rows_ok(int n, int c, i64 ld) { return n > 0 && c > 0 && ld >= c; }
+
+}  // namespace
+
+extern "C" {
+
+int rnnpose_point_row_sum_f32(const float* x, int n, int c, long long ldx, float* out, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_row_sum_f32";
+  RP_REQUIRE(x && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n, c, ldx), fn, "bad size (n, c > 0, ldx >= c)");
+  hipLaunchKernelGGL(row_sum_kernel, dim3(rp::cdiv(static_cast<i64>(n) * 64, 256)), dim3(256), 0, rp::as_stream(stream), x, n, c, ldx,
+                     out);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_kpconv_aggregate_f32(const float* q_pts, int n_q, const float* s_pts, int n_s, const int* neighbors, int width,
+                                 const float* kernel_points, int K, float extent, const float* x, int c_in, long long ldx,
+                                 const float* row_sum, float* wf, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_kpconv_aggregate_f32";
+  RP_REQUIRE(q_pts && s_pts && neighbors && kernel_points && x && row_sum && wf, fn, "null pointer");
+  RP_REQUIRE(n_q > 0 && n_s > 0 && width > 0, fn, "bad size (n_q, n_s, width > 0)");
+  RP_REQUIRE(K > 0 && K <= KP_MAX, fn, "K must be in 1..16");
+  RP_REQUIRE(c_in > 0 && c_in <= 256 && ldx >= c_in, fn, "c_in must be in 1..256 (ldx >= c_in)");
+  RP_REQUIRE(extent > 0.f, fn, "extent must be positive");
+  RP_REQUIRE(static_cast<i64>(K) * c_in * n_q < (1LL << 40), fn, "output too large");
+  const dim3 grid(rp::cdiv(n_q, 4)), block(256);
+  hipStream_t s = rp::as_stream(stream);
+  if (c_in <= 64)
+    hipLaunchKernelGGL(kpconv_aggregate_kernel<1>, grid, block, 0, s, q_pts, s_pts, n_q, n_s, neighbors, width, kernel_points, K, extent,
+                       x, c_in, ldx, row_sum, wf);
+  else if (c_in <= 128)
+    hipLaunchKernelGGL(kpconv_aggregate_kernel<2>, grid, block, 0, s, q_pts, s_pts, n_q, n_s, neighbors, width, kernel_points, K, extent,
+                       x, c_in, ldx, row_sum, wf);
+  else
+    hipLaunchKernelGGL(kpconv_aggregate_kernel<4>, grid, block, 0, s, q_pts, s_pts, n_q, n_s, neighbors, width, kernel_points, K, extent,
+                       x, c_in, ldx, row_sum, wf);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_point_linear_f32(const float* a, int n, int k, long long lda, const float* w, int m, const float* bias, float* out,
+                             long long ldo, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_linear_f32";
+  RP_REQUIRE(a && w && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n, k, lda) && m > 0 && ldo >= m, fn, "bad size (n, k, m > 0, lda >= k, ldo >= m)");
+  hipStream_t s = rp::as_stream(stream);
+  if (n >= 64 * 256)
+    hipLaunchKernelGGL(point_linear_kernel<64>, dim3(rp::cdiv(m, 64), rp::cdiv(n, 64)), dim3(256), 0, s, a, lda, n, k, w, m, bias, out,
+                       ldo);
+  else
+    hipLaunchKernelGGL(point_linear_kernel<16>, dim3(rp::cdiv(m, 64), rp::cdiv(n, 16)), dim3(256), 0, s, a, lda, n, k, w, m, bias, out,
+                       ldo);
+  return rp::check_launch(fn);
+}
+
+long long rnnpose_point_norm_workspace_bytes(int n, int c) {
+  if (n <= 0 || c <= 0) return 0;
+  return static_cast<long long>(rp::cdiv(n, NORM_CHUNK_ROWS)) * c * 2 * sizeof(double);
+}
+
+int rnnpose_point_norm_stats_f32(const float* x, int n, int c, long long ldx, float eps, void* workspace, long long workspace_bytes,
+                                 float* mean_rstd, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_norm_stats_f32";
+  RP_REQUIRE(x && workspace && mean_rstd, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n, c, ldx), fn, "bad size (n, c > 0, ldx >= c)");
+  RP_REQUIRE(workspace_bytes >= rnnpose_point_norm_workspace_bytes(n, c), fn, "workspace smaller than rnnpose_point_norm_workspace_bytes");
+  const int chunks = rp::cdiv(n, NORM_CHUNK_ROWS);
+  hipStream_t s = rp::as_stream(stream);
+  double* ws = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(norm_partial_kernel, dim3(rp::cdiv(c, 64), chunks), dim3(256), 0, s, x, ldx, n, c, ws);
+  hipLaunchKernelGGL(norm_final_kernel, dim3(rp::cdiv(c, 256)), dim3(256), 0, s, ws, chunks, n, c, eps, mean_rstd);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_point_norm_apply_f32(const float* x, int n, int c, long long ldx, const float* mean_rstd, const float* res, long long ldr,
+                                 const float* res_mean_rstd, int leaky, float slope, float* out, long long ldo,
+                                 rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_norm_apply_f32";
+  RP_REQUIRE(x && mean_rstd && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n, c, ldx) && ldo >= c && (!res || ldr >= c), fn, "bad size (n, c > 0, strides >= c)");
+  RP_REQUIRE(!res_mean_rstd || res, fn, "res_mean_rstd without res");
+  hipLaunchKernelGGL(norm_apply_kernel, dim3(rp::cdiv(static_cast<i64>(n) * c, 256)), dim3(256), 0, rp::as_stream(stream), x, ldx, n, c,
+                     mean_rstd, res, ldr, res_mean_rstd, leaky, slope, out, ldo);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_point_maxpool_f32(const float* x, int n_s, int c, long long ldx, const int* idx, int n_q, int width, float* out,
+                              long long ldo, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_maxpool_f32";
+  RP_REQUIRE(x && idx && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n_s, c, ldx) && n_q > 0 && width > 0 && ldo >= c, fn, "bad size (n_s, n_q, c, width > 0, strides >= c)");
+  hipLaunchKernelGGL(point_maxpool_kernel, dim3(rp::cdiv(static_cast<i64>(n_q) * c, 256)), dim3(256), 0, rp::as_stream(stream), x, ldx,
+                     n_s, c, idx, n_q, width, out, ldo);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_point_gather_rows_f32(const float* x, int n_s, int c, long long ldx, const int* idx, int n_q, int idx_ld, float* out,
+                                  long long ldo, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_gather_rows_f32";
+  RP_REQUIRE(x && idx && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n_s, c, ldx) && n_q > 0 && idx_ld > 0 && ldo >= c, fn, "bad size (n_s, n_q, c, idx_ld > 0, strides >= c)");
+  hipLaunchKernelGGL(point_gather_kernel, dim3(rp::cdiv(static_cast<i64>(n_q) * c, 256)), dim3(256), 0, rp::as_stream(stream), x, ldx,
+                     n_s, c, idx, idx_ld, n_q, out, ldo);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_point_l2_normalize_f32(const float* x, int n, int c, long long ldx, float* out, long long ldo, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_l2_normalize_f32";
+  RP_REQUIRE(x && out, fn, "null pointer");
+  RP_REQUIRE(rows_ok(n, c, ldx) && ldo >= c, fn, "bad size (n, c > 0, strides >= c)");
+  hipLaunchKernelGGL(l2_rows_kernel, dim3(rp::cdiv(static_cast<i64>(n) * 64, 256)), dim3(256), 0, rp::as_stream(stream), x, ldx, n, c,
+                     out, ldo);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_grid_voxel_keys_f32(const float* points, int n, float ox, float oy, float oz, float dl, long long nx, long long ny,
+                                long long* keys, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_grid_voxel_keys_f32";
+  RP_REQUIRE(points && keys, fn, "null pointer");
+  RP_REQUIRE(n > 0 && dl > 0.f && nx > 0 && ny > 0, fn, "bad size (n, nx, ny > 0, dl > 0)");
+  hipLaunchKernelGGL(grid_keys_kernel, dim3(rp::cdiv(n, 256)), dim3(256), 0, rp::as_stream(stream), points, n, ox, oy, oz, dl, nx, ny,
+                     reinterpret_cast<i64*>(keys));
+  return rp::check_launch(fn);
+}
+
+int rnnpose_radius_count_f32(const float* queries, int n_q, const float* supports, const int* q_start, const int* s_start,
+                             int n_clouds, float radius, int* counts, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_radius_count_f32";
+  RP_REQUIRE(queries && supports && q_start && s_start && counts, fn, "null pointer");
+  RP_REQUIRE(n_q > 0 && n_clouds > 0, fn, "bad size (n_q, n_clouds > 0)");
+  hipLaunchKernelGGL(radius_kernel<0>, dim3(rp::cdiv(n_q, 256)), dim3(256), 0, rp::as_stream(stream), queries, n_q, supports, q_start,
+                     s_start, n_clouds, radius, counts, nullptr, nullptr, nullptr, 0, nullptr);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_radius_neighbors_f32(const float* queries, int n_q, const float* supports, const int* q_start, const int* s_start,
+                                 int n_clouds, float radius, const long long* offsets, int* cand_idx, float* cand_d2, int width,
+                                 int* out, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_radius_neighbors_f32";
+  RP_REQUIRE(queries && supports && q_start && s_start && offsets && cand_idx && cand_d2 && out, fn, "null pointer");
+  RP_REQUIRE(n_q > 0 && n_clouds > 0 && width > 0, fn, "bad size (n_q, n_clouds, width > 0)");
+  hipLaunchKernelGGL(radius_kernel<1>, dim3(rp::cdiv(n_q, 256)), dim3(256), 0, rp::as_stream(stream), queries, n_q, supports, q_start,
+                     s_start, n_clouds, radius, nullptr, reinterpret_cast<const i64*>(offsets), cand_idx, cand_d2, width, out);
+  return rp::check_launch(fn);
+}
+
+}  // extern "C"

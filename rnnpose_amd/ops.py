@@ -1230,6 +1230,247 @@ def pixel_head_nhwc(src, weight, bias, mode: int = PH_LINEAR, src_c_offset: int 
     return out
 
 
+# ---- KPSuperpoint3Dv2 (model/descriptor3D.py, thirdparty/kpconv; rnnpose_amd/descriptor3d.py) ---------------------------------
+def _rows(t, name, cols=None):
+    """A (N, C) fp32 CUDA matrix whose rows may be strided (a channel slice of a wider buffer): returns its row stride."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == F32 and t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1)):
+        raise ValueError(f"{name} must be a 2-D fp32 CUDA tensor with unit column stride")
+    if cols is not None and t.shape[1] != cols:
+        raise ValueError(f"{name} must have {cols} columns, got {t.shape[1]}")
+    if t.shape[0] == 0 or t.shape[1] == 0:
+        raise ValueError(f"{name} is empty")
+    return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def _points(p, name):
+    if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == F32 and p.is_contiguous() and p.dim() == 2 and p.shape[1] == 3):
+        raise ValueError(f"{name} must be a contiguous (N, 3) fp32 CUDA tensor")
+    return p
+
+
+def neighbor_table(idx, n_s, name="neighbors"):
+    """int32 contiguous copy of an (n_q, width) neighbour table (int32 or int64) after checking every value is in 0..n_s
+    (n_s = the shadow neighbour)."""
+    if not (isinstance(idx, torch.Tensor) and idx.dim() == 2 and idx.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"{name} must be a 2-D int32 or int64 tensor")
+    if idx.shape[0] == 0 or idx.shape[1] == 0:
+        raise ValueError(f"{name} is empty")
+    if not idx.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {idx.device}); rnnpose_amd has no CPU path")
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi > n_s:
+        raise ValueError(f"{name}: indices must lie in 0..{n_s} ({n_s} = the shadow neighbour), got {lo}..{hi}")
+    return idx.to(torch.int32).contiguous()
+
+
+def point_row_sum(x, out=None):
+    """out[i] = sum_c x[i, c] (fp32): the positive-sum test of KPConv's neighbour count (kpconv_blocks.py:366-369)."""
+    ld = _rows(x, "x")
+    n, c = x.shape
+    if out is None:
+        out = torch.empty(n, device=x.device, dtype=F32)
+    _launch("rnnpose_point_row_sum_f32", _ptr(x), n, c, ld, _ptr(out), _stream(), work=n * c, nbytes=4.0 * n * (c + 1))
+    return out
+
+
+def kpconv_aggregate(q_pts, s_pts, neighbors, kernel_points, extent: float, x, row_sum=None, out=None):
+    """KPConv.forward (kpconv_blocks.py:300-372: linear influence, sum aggregation) up to the weight product:
+    (n_q, K * c_in) with column k * c_in + c = sum_j infl_kj x[j, c] / max(1, #{j : sum_c x[j, c] > 0}).
+    neighbors: an int32 table from neighbor_table (values 0..n_s); x (n_s, c_in) rows may be strided."""
+    _points(q_pts, "q_pts")
+    _points(s_pts, "s_pts")
+    ld = _rows(x, "x")
+    n_s, c_in = x.shape
+    if s_pts.shape[0] != n_s:
+        raise ValueError(f"x has {n_s} rows for {s_pts.shape[0]} support points")
+    if not (neighbors.dtype == torch.int32 and neighbors.is_contiguous() and neighbors.dim() == 2 and neighbors.shape[0] == q_pts.shape[0]):
+        raise ValueError("neighbors must be a contiguous int32 (n_q, width) table (ops.neighbor_table)")
+    kp = _chk(kernel_points.detach(), "kernel_points")
+    K = kp.shape[0]
+    if tuple(kp.shape) != (K, 3):
+        raise ValueError("kernel_points must be (K, 3)")
+    n_q, width = neighbors.shape
+    if row_sum is None:
+        row_sum = point_row_sum(x)
+    if out is None:
+        out = torch.empty(n_q, K * c_in, device=x.device, dtype=F32)
+    if not (out.is_contiguous() and tuple(out.shape) == (n_q, K * c_in) and out.dtype == F32):
+        raise ValueError(f"out must be a contiguous fp32 ({n_q}, {K * c_in}) tensor")
+    _launch("rnnpose_kpconv_aggregate_f32", _ptr(q_pts), n_q, _ptr(s_pts), n_s, _ptr(neighbors), width, _ptr(kp), K, float(extent),
+            _ptr(x), c_in, ld, _ptr(row_sum), _ptr(out), _stream(), work=2.0 * n_q * width * K * (c_in + 6),
+            nbytes=4.0 * n_q * (width * (c_in + 5) + K * c_in))
+    return out
+
+
+def point_linear(a, w, bias=None, out=None):
+    """out (n, m) = a (n, k) @ w (k, m) (+ bias (m,)): fp32 FMA in k order.  a's and out's rows may be strided (channel slices)."""
+    lda = _rows(a, "a")
+    n, k = a.shape
+    wt = _chk(w.detach(), "w")
+    if wt.dim() != 2 or wt.shape[0] != k:
+        raise ValueError(f"w must be ({k}, m), got {tuple(wt.shape)}")
+    m = wt.shape[1]
+    b = None
+    if bias is not None:
+        b = _chk(bias.detach(), "bias")
+        if tuple(b.shape) != (m,):
+            raise ValueError(f"bias must be ({m},)")
+    if out is None:
+        out = torch.empty(n, m, device=a.device, dtype=F32)
+    ldo = _rows(out, "out", m)
+    if out.shape[0] != n:
+        raise ValueError(f"out must have {n} rows")
+    _launch("rnnpose_point_linear_f32", _ptr(a), n, k, lda, _ptr(wt), m, _ptr(b), _ptr(out), ldo, _stream(), work=2.0 * n * k * m,
+            nbytes=4.0 * (n * (k + m) + k * m))
+    return out
+
+
+def point_norm_stats(x, eps: float = 1e-5):
+    """InstanceNorm1d statistics over ALL rows of x (n, c) (BatchNormBlock, kpconv_blocks.py:456-473): (c, 2) fp32 (mean, rstd)."""
+    ld = _rows(x, "x")
+    n, c = x.shape
+    nb = int(_lib.load().rnnpose_point_norm_workspace_bytes(n, c))
+    ws = torch.empty(max(1, nb // 8), device=x.device, dtype=F64)
+    mr = torch.empty(c, 2, device=x.device, dtype=F32)
+    _launch("rnnpose_point_norm_stats_f32", _ptr(x), n, c, ld, float(eps), _ptr(ws), nb, _ptr(mr), _stream(), work=3.0 * n * c,
+            nbytes=4.0 * n * c)
+    return mr
+
+
+def point_norm_apply(x, mean_rstd, leaky: bool = True, res=None, res_mean_rstd=None, slope: float = 0.1, out=None):
+    """out = (x - mean) * rstd [+ res (normalised by res_mean_rstd if given)] [LeakyReLU(slope)]; out may be x or a channel slice."""
+    ld = _rows(x, "x")
+    n, c = x.shape
+    mr = _chk(mean_rstd, "mean_rstd")
+    if tuple(mr.shape) != (c, 2):
+        raise ValueError(f"mean_rstd must be ({c}, 2)")
+    ldr, rmr = 0, None
+    if res is not None:
+        ldr = _rows(res, "res", c)
+        if res.shape[0] != n:
+            raise ValueError(f"res must have {n} rows")
+        if res_mean_rstd is not None:
+            rmr = _chk(res_mean_rstd, "res_mean_rstd")
+            if tuple(rmr.shape) != (c, 2):
+                raise ValueError(f"res_mean_rstd must be ({c}, 2)")
+    elif res_mean_rstd is not None:
+        raise ValueError("res_mean_rstd without res")
+    if out is None:
+        out = torch.empty(n, c, device=x.device, dtype=F32)
+    ldo = _rows(out, "out", c)
+    if out.shape[0] != n:
+        raise ValueError(f"out must have {n} rows")
+    _launch("rnnpose_point_norm_apply_f32", _ptr(x), n, c, ld, _ptr(mr), _ptr(res), ldr, _ptr(rmr), int(bool(leaky)), float(slope),
+            _ptr(out), ldo, _stream(), work=4.0 * n * c, nbytes=4.0 * n * c * (2 + (res is not None)))
+    return out
+
+
+def point_maxpool(x, idx, out=None):
+    """max_pool (kpconv_blocks.py:88-104): out[q] = max over idx[q, :] of the rows of x, the shadow index (n_s) a zero row."""
+    ld = _rows(x, "x")
+    n_s, c = x.shape
+    if not (idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2):
+        raise ValueError("idx must be a contiguous int32 table (ops.neighbor_table)")
+    n_q, width = idx.shape
+    if out is None:
+        out = torch.empty(n_q, c, device=x.device, dtype=F32)
+    ldo = _rows(out, "out", c)
+    if out.shape[0] != n_q:
+        raise ValueError(f"out must have {n_q} rows")
+    _launch("rnnpose_point_maxpool_f32", _ptr(x), n_s, c, ld, _ptr(idx), n_q, width, _ptr(out), ldo, _stream(), work=n_q * width * c,
+            nbytes=4.0 * n_q * c * (width + 1))
+    return out
+
+
+def point_gather_rows(x, idx, out=None):
+    """closest_pool (kpconv_blocks.py:73-85): out[q] = x[idx[q, 0]], zeros for the shadow index (n_s)."""
+    ld = _rows(x, "x")
+    n_s, c = x.shape
+    if not (idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 2):
+        raise ValueError("idx must be a contiguous int32 table (ops.neighbor_table)")
+    n_q = idx.shape[0]
+    if out is None:
+        out = torch.empty(n_q, c, device=x.device, dtype=F32)
+    ldo = _rows(out, "out", c)
+    if out.shape[0] != n_q:
+        raise ValueError(f"out must have {n_q} rows")
+    _launch("rnnpose_point_gather_rows_f32", _ptr(x), n_s, c, ld, _ptr(idx), n_q, idx.shape[1], _ptr(out), ldo, _stream(),
+            work=n_q * c, nbytes=8.0 * n_q * c)
+    return out
+
+
+def point_l2_normalize(x, out=None):
+    """F.normalize(x, p=2, dim=1, eps=1e-12) row by row (model/descriptor3D.py:134-136); out may be x."""
+    ld = _rows(x, "x")
+    n, c = x.shape
+    if out is None:
+        out = torch.empty(n, c, device=x.device, dtype=F32)
+    ldo = _rows(out, "out", c)
+    if out.shape[0] != n:
+        raise ValueError(f"out must have {n} rows")
+    _launch("rnnpose_point_l2_normalize_f32", _ptr(x), n, c, ld, _ptr(out), ldo, _stream(), work=3.0 * n * c, nbytes=8.0 * n * c)
+    return out
+
+
+def grid_voxel_keys(points, origin, dl, nx: int, ny: int):
+    """Voxel keys of grid_subsampling.cpp:50-56: ix + nx iy + nx ny iz, ix = floor((p.x - origin.x) / dl) in fp32 (correctly
+    rounded division), for (N, 3) points of one cloud -> int64 (N,).  origin: 3 floats (fp32 values), dl: fp32 value."""
+    _points(points, "points")
+    n = points.shape[0]
+    keys = torch.empty(n, device=points.device, dtype=torch.int64)
+    if n == 0:
+        return keys
+    ox, oy, oz = (float(v) for v in origin)
+    _launch("rnnpose_grid_voxel_keys_f32", _ptr(points), n, ox, oy, oz, float(dl), int(nx), int(ny), _ptr(keys), _stream(), work=9.0 * n,
+            nbytes=20.0 * n)
+    return keys
+
+
+def _starts(lengths, n, dev, name):
+    ln = [int(v) for v in lengths]
+    if any(v < 0 for v in ln) or sum(ln) != n:
+        raise ValueError(f"{name} must be non-negative and sum to {n}, got {ln}")
+    st = [0]
+    for v in ln:
+        st.append(st[-1] + v)
+    return torch.tensor(st, device=dev, dtype=torch.int32)
+
+
+def radius_neighbors(queries, supports, q_lengths, s_lengths, radius: float, limit=None):
+    """batch_neighbors_kpconv (data/preprocess.py:544-561 on cpp_neighbors/neighbors/neighbors.cpp:229-330): for each query, the
+    supports of ITS cloud (stacked lengths) with ((dx^2 + dy^2) + dz^2) < radius^2 in fp32, sorted by (d2, index); the table is
+    min(limit, largest count) wide (limit None or <= 0: no truncation) and padded with len(supports).  -> int64 (n_q, width)."""
+    _points(queries, "queries")
+    _points(supports, "supports")
+    n_q, n_s = queries.shape[0], supports.shape[0]
+    if len(q_lengths) != len(s_lengths):
+        raise ValueError("q_lengths and s_lengths must have one entry per cloud")
+    dev = queries.device
+    qs, ss = _starts(q_lengths, n_q, dev, "q_lengths"), _starts(s_lengths, n_s, dev, "s_lengths")
+    B = len(q_lengths)
+    if n_q == 0:
+        return torch.zeros(0, 1, device=dev, dtype=torch.int64)
+    counts = torch.empty(n_q, device=dev, dtype=torch.int32)
+    if n_s == 0:
+        counts.zero_()
+    else:
+        _launch("rnnpose_radius_count_f32", _ptr(queries), n_q, _ptr(supports), _ptr(qs), _ptr(ss), B, float(radius), _ptr(counts),
+                _stream(), work=9.0 * n_q * n_s / B, nbytes=12.0 * (n_q + n_s))
+    max_count = int(counts.max())
+    width = max_count if (limit is None or limit <= 0) else min(int(limit), max_count)
+    out = torch.full((n_q, max(width, 1)), n_s, device=dev, dtype=torch.int32)
+    if width == 0:
+        return out[:, :0].long()
+    offsets = torch.zeros(n_q, device=dev, dtype=torch.int64)
+    offsets[1:] = torch.cumsum(counts.long(), 0)[:-1]
+    total = int(offsets[-1]) + int(counts[-1])
+    cand_idx = torch.empty(total, device=dev, dtype=torch.int32)
+    cand_d2 = torch.empty(total, device=dev, dtype=F32)
+    _launch("rnnpose_radius_neighbors_f32", _ptr(queries), n_q, _ptr(supports), _ptr(qs), _ptr(ss), B, float(radius), _ptr(offsets),
+            _ptr(cand_idx), _ptr(cand_d2), width, _ptr(out), _stream(), work=9.0 * n_q * n_s / B, nbytes=12.0 * (n_q + n_s) + 8.0 * total)
+    return out.long()
+
+
 # ---- f2/f3: evaluator metrics ------------------------------------------------------------------------------------
 def nn_search(ref_pts, que_pts, exclude_self: bool = False):
     """ref (B,N1,D), que (B,N2,D) fp32 on the GPU, D in {2,3} -> idx (B,N2) int32: first nearest reference point."""
