@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs bench_outputs   # + the last timed step's outputs as .npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full     # + CPU baseline and in-run parity against the CPU oracle
     python bench.py --gpus 8                       # no WORLD_SIZE in the environment: spawns the 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -15,19 +16,22 @@ weight -> LM step.  The renderer is outside the path: vie
 Inputs are resident in HBM before the timed region.  value = refinement iterations/s (one iteration = the
 loop body for one rank's batch of 8), summed over ranks (weak scaling: every rank refines its own batch).
 
-Rank 0 prints ONE JSON line (see the task contract) carrying
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; whatever needs runs of its own
+(the CPU baseline and the parity gate, together about 85 s at the default size) is done only with --full, after the line's
+figures are taken.  Rank 0 prints ONE JSON line (see the task contract) carrying
   roofline                   the dominant kernel (the implicit-GEMM convolution) against the fp16 MFMA peak, per launch,
                              measured live with HIP events on the launch stream;
   chip_level                 executed matrix-core flops of the WHOLE step / wall time of the step;
   correlation_volume_kernel  north_star's named kernel against the HBM roofline;
   kernels                    every C-ABI launch type: mean duration, share of the step, achieved GB/s from the bytes each
                              launch declared for its own arguments (a half-batch launch declares half the batch);
-  cpu_baseline               the CPU oracle on this box's host cores: the full batch, 1 outer x `inner` iterations (the 3x8
-                             schedule repeats that unit, so iterations/s are directly comparable), median of 3 runs, N=1 only;
-  parity                     the GPU refiner's first outer iteration against that oracle run's outputs (identical inputs, both
-                             started from the reference's literal Tij = Ti * Ti^-1 -- the shipped default since r06): pose within
-                             1e-5 and first-iteration flow within 1e-4, or the line is declared invalid; `exact_identity_start` =
-                             the same gate for the literal_legacy_pose=False option.
+  cpu_baseline               --full only (null otherwise): the CPU oracle on the host cores: the full batch, 1 outer x `inner`
+                             iterations (the 3x8 schedule repeats that unit, so iterations/s are directly comparable), median of
+                             3 runs, N=1 only;
+  parity                     --full only (null otherwise): the GPU refiner's first outer iteration against that oracle run's
+                             outputs (identical inputs, both started from the reference's literal Tij = Ti * Ti^-1 -- the
+                             shipped default since r06): pose within 1e-5 and first-iteration flow within 1e-4, or the line is
+                             declared invalid; `exact_identity_start` = the same gate for the literal_legacy_pose=False option.
 """
 from __future__ import annotations
 
@@ -60,8 +64,11 @@ def parse():
     ap.add_argument("--outer", type=int, default=3)
     ap.add_argument("--inner", type=int, default=8)
     ap.add_argument("--optim-iters", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-runs", type=int, default=3, help="timed runs of the CPU baseline (median reported) after one warm-up run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline and the parity gate against the CPU oracle (N=1 only); a plain "
+                         "run leaves both out of the line (null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the parity gate")
+    ap.add_argument("--cpu-runs", type=int, default=3, help="--full: timed runs of the CPU baseline (median reported) after one warm-up run")
     ap.add_argument("--no-encoder", action="store_true", help="feed synthetic feature maps (kernel-only runs)")
     ap.add_argument("--unfused", action="store_true", help="literal reference call sequence through the facade")
     ap.add_argument("--no-graph", action="store_true", help="eager launches only (no hipGraph replay; for counter passes)")
@@ -505,7 +512,7 @@ def main():
                         "encoder run on two streams in the timed steps, and so do the two batch halves of the loop, so the "
                         "shares, measured launch by launch on one stream, can add up to more than 1)",
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"], want = cpu_baseline(refiner, rend, K, G0, args)
         res["speedup_vs_cpu"] = round(value / res["cpu_baseline"]["value"], 1)
         res["parity"] = parity_block(refiner, rend, K, G0, args, want)

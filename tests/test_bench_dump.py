@@ -74,3 +74,11 @@ def test_bench_steps_argument_is_taken_as_given(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "0", "--dump-outputs", "d"])
     a = bench.parse()
     assert (a.steps, a.warmup, a.dump_outputs) == (3, 0, "d")
+
+
+def test_bench_leaves_the_cpu_baseline_and_parity_to_full(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--full"])
+    a = bench.parse()
+    assert a.full is True and (a.steps, a.warmup) == (3, 1)

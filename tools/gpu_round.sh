@@ -26,7 +26,7 @@ tail -5 $OUT/${TAG}_pytest_gpu.log
 python __graft_entry__.py smoke > $OUT/${TAG}_smoke.log 2>&1; tail -2 $OUT/${TAG}_smoke.log
 B="python bench.py --no-cpu-baseline"
 if [ "$MODE" = "noprof" ]; then
-  python bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+  python bench.py --steps 20 --warmup 3 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
   tail -c 300 $OUT/${TAG}_bench.err; head -c 300 $OUT/${TAG}_bench.json; echo
   exit 0
 fi
@@ -42,7 +42,7 @@ else
 fi
 python tools/summarize_profiles.py $TAG $OUT/${TAG}_summary > $OUT/${TAG}_summary.log 2>&1
 [ -f $OUT/${TAG}_summary/traffic.json ] && cp $OUT/${TAG}_summary/traffic.json profiles/traffic.json
-python bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --steps 20 --warmup 3 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 300 $OUT/${TAG}_bench.err; head -c 300 $OUT/${TAG}_bench.json; echo
 RNNPOSE_SPLIT_BATCH=0 RNNPOSE_ENCODER_MERGE=1 $B --steps 20 --warmup 3 > $OUT/${TAG}_bench_one_stream.json 2>/dev/null     # r04's default: one chain, one stream
 $B --steps 20 --warmup 3 --batch 1 --height 240 --width 240 --inner 4 > $OUT/${TAG}_bench_S1.json 2>/dev/null
