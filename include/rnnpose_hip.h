@@ -606,6 +606,25 @@ int rnnpose_raster_resolve_f32(const float* verts, const int* faces, const int* 
                                const void* workspace, const float* attr, const long long* attr_off, int C,
                                const float* colors, int with_color, int shade, float empty_depth, float* out_attr,
                                float* out_zbuf, float* out_vdepth, rnnpose_stream_t stream);
+/* rnnpose_raster_resolve_tex_f32: pass 2 of a textured, per-pixel shaded render (DiffRender.render_mesh: TexturesUV on
+ *   SoftPhongShader, faces_per_pixel = 1).  Workspace, geometry, attr and the three outputs as rnnpose_raster_resolve_f32 with
+ *   with_color = 1 (out_attr has 3 + C channels).  The albedo of a pixel of image b:
+ *     tex_hw[b] = (th, tw) > 0: the texture at uv = sum w_i uv_i (same barycentrics as the attributes), sampled as
+ *       grid_sample(flip(map, H), uv * 2 - 1, bilinear, align_corners = True, padding_mode = border) -- uvs (U,2) of all meshes
+ *       back to back, image b's start at row uv_off[b]; face_uvs (F,3) int32 = LOCAL uv indices, row for row with faces; tex =
+ *       RGBA fp32 texels (16-byte aligned), image b's map starts at texel tex_off[b] (int64) with its th rows stored already
+ *       flipped (row 0 = the image's bottom row);
+ *     tex_hw[b] = (0,0) or tex NULL: the interpolated vertex colours, white if colors is NULL.
+ *   shade 0: the albedo; 1: the flat two-sided terms of rnnpose_raster_resolve_f32; 2: PyTorch3D phong_shading at its
+ *   defaults with shininess 0 and a point light at (1,1,-1) in object space: (0.5 + 0.3 relu(n.l)) * albedo + 0.2, n = the
+ *   interpolated vnormals (V,3, aligned with verts) normalised with eps 1e-6, l = normalize((1,1,-1) - p, eps 1e-6). */
+int rnnpose_raster_resolve_tex_f32(const float* verts, const int* faces, const int* vert_off, const int* face_off, const float* T,
+                                   const float* K, int B, int H, int W, float near, float pixel_center, int perspective_correct,
+                                   const void* workspace, const float* attr, const long long* attr_off, int C,
+                                   const float* colors, const float* uvs, const int* face_uvs, const int* uv_off, const float* tex,
+                                   const long long* tex_off, const int* tex_hw, const float* vnormals, int shade,
+                                   float empty_depth, float* out_attr, float* out_zbuf, float* out_vdepth,
+                                   rnnpose_stream_t stream);
 
 #ifdef __cplusplus
 }

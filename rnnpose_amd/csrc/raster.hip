@@ -15,6 +15,9 @@
 //      SAME arithmetic as pass 1 and writes depth, nearest-vertex depth and the interpolated vertex attributes
 //      ([shaded colour |] C channels, NCHW planes: consecutive lanes are consecutive x -> coalesced plane writes; every
 //      lane walks its three attribute rows 16 bytes at a time).
+//   2'. raster_resolve_tex_kernel (render_tex with a UV texture or Phong shading): the same pass, with the colour taken from
+//      the mesh's texture map at the interpolated UV (one bilinear grid_sample, four 16-byte RGBA taps) and shaded per pixel
+//      with interpolated vertex normals (PyTorch3D's SoftPhongShader with faces_per_pixel = 1).
 #include "common.hpp"
 
 namespace {
@@ -204,6 +207,152 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const float* __rest
   for (; c < C; ++c) o[c * P] = hit ? w0 * a0[c] + w1 * a1[c] + w2 * a2[c] : 0.f;
 }
 
+// grid_sample(map, g, mode="bilinear", align_corners=True, padding_mode="border") at one point of the pre-flipped RGBA map
+// `tex` (th rows of tw texels): the arithmetic of PyTorch's grid sampler step by step -- unnormalise ((g+1)/2)*(size-1), clip
+// to [0, size-1], four taps weighted from the floor corner.  A tap at x = tw or y = th has weight 0 and is not read.
+__device__ __forceinline__ float4 sample_bilinear_border(const float4* __restrict__ tex, int th, int tw, float gx, float gy) {
+#pragma clang fp contract(off)
+  float ix = ((gx + 1.f) / 2.f) * static_cast<float>(tw - 1);
+  float iy = ((gy + 1.f) / 2.f) * static_cast<float>(th - 1);
+  ix = fminf(static_cast<float>(tw - 1), fmaxf(ix, 0.f));     // (fmaxf(NaN, 0) = 0: a NaN coordinate samples the corner)
+  iy = fminf(static_cast<float>(th - 1), fmaxf(iy, 0.f));
+  const float fx = floorf(ix), fy = floorf(iy);
+  const int x0 = static_cast<int>(fx), y0 = static_cast<int>(fy);
+  const float x1f = fx + 1.f, y1f = fy + 1.f;
+  const float wnw = (x1f - ix) * (y1f - iy), wne = (ix - fx) * (y1f - iy);
+  const float wsw = (x1f - ix) * (iy - fy), wse = (ix - fx) * (iy - fy);
+  const bool xin = x0 + 1 < tw, yin = y0 + 1 < th;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4* r0 = tex + static_cast<long long>(y0) * tw;
+  const float4 nw = r0[x0];
+  const float4 ne = xin ? r0[x0 + 1] : z4;
+  const float4 sw = yin ? r0[tw + x0] : z4;
+  const float4 se = (xin && yin) ? r0[tw + x0 + 1] : z4;
+  return make_float4(((nw.x * wnw + ne.x * wne) + sw.x * wsw) + se.x * wse, ((nw.y * wnw + ne.y * wne) + sw.y * wsw) + se.y * wse,
+                     ((nw.z * wnw + ne.z * wne) + sw.z * wsw) + se.z * wse, 0.f);
+}
+
+// The textured resolve: raster_resolve_kernel's depth / nearest-vertex depth / attribute channels, and in front of them an RGB
+// image whose albedo is the mesh's texture sampled at the interpolated UV (TexturesUV.sample_textures), or its vertex colours
+// (white without them) when the image's mesh has no texture, shaded by `shade`: 0 none, 1 the flat two-sided terms of
+// raster_resolve_kernel, 2 PyTorch3D's phong_shading with interpolated vertex normals.
+__global__ __launch_bounds__(256) void raster_resolve_tex_kernel(
+    const float* __restrict__ verts, const int* __restrict__ faces, const int* __restrict__ vert_off, const int* __restrict__ face_off,
+    const float* __restrict__ T, const float* __restrict__ K, int H, int W, float near, float pix_center, int perspective,
+    const unsigned long long* __restrict__ zb, const float* __restrict__ attr, const long long* __restrict__ attr_off, int C,
+    const float* __restrict__ colors, const float* __restrict__ uvs, const int* __restrict__ face_uvs, const int* __restrict__ uv_off,
+    const float4* __restrict__ tex, const long long* __restrict__ tex_off, const int* __restrict__ tex_hw,
+    const float* __restrict__ vnormals, int shade, float empty_depth, float* __restrict__ out_attr, float* __restrict__ out_zbuf,
+    float* __restrict__ out_vdepth) {
+  const int b = blockIdx.y;
+  const long long P = static_cast<long long>(H) * W;
+  const long long pix = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (pix >= P) return;
+  const int x = static_cast<int>(pix % W), y = static_cast<int>(pix / W);
+  const unsigned long long key = zb[b * P + pix];
+  const bool hit = key != kEmpty;
+  float w0 = 0.f, w1 = 0.f, w2 = 0.f, z = 0.f;
+  int v0 = 0, v1 = 0, v2 = 0;
+  long long f = 0;
+  Tri t{};
+  const int vb = vert_off[b];
+  if (hit) {
+    const Cam c = load_cam(T, K, b);
+    f = static_cast<long long>(face_off[b]) + static_cast<unsigned>(key & 0xffffffffull);
+    t = project_face(verts, faces, f, vb, c, near);
+    bary_at(t, static_cast<float>(x) + pix_center, static_cast<float>(y) + pix_center, perspective, w0, w1, w2, z);
+    v0 = faces[3 * f + 0]; v1 = faces[3 * f + 1]; v2 = faces[3 * f + 2];
+  }
+  if (out_zbuf) out_zbuf[b * P + pix] = hit ? z : empty_depth;
+  if (out_vdepth) {
+    float vz = 0.f;
+    if (hit) vz = (w0 >= w1 && w0 >= w2) ? t.z[0] : (w1 >= w2 ? t.z[1] : t.z[2]);
+    out_vdepth[b * P + pix] = vz;
+  }
+  if (!out_attr) return;
+  float* o = out_attr + static_cast<long long>(b) * (3 + C) * P + pix;
+  float col[3] = {0.f, 0.f, 0.f};
+  if (hit) {                                       // (no contraction here: the colour is PyTorch3D's op-by-op fp32 arithmetic)
+#pragma clang fp contract(off)
+    const int th = tex ? tex_hw[2 * b] : 0, tw = tex ? tex_hw[2 * b + 1] : 0;
+    float alb[3] = {1.f, 1.f, 1.f};
+    if (th > 0 && tw > 0) {                        // TexturesUV: uv = sum w_i uv_i, grid = uv * 2 - 1 on the flipped map
+      const float* uvb = uvs + 2LL * uv_off[b];
+      const float* t0 = uvb + 2LL * face_uvs[3 * f + 0];
+      const float* t1 = uvb + 2LL * face_uvs[3 * f + 1];
+      const float* t2 = uvb + 2LL * face_uvs[3 * f + 2];
+      const float u = (w0 * t0[0] + w1 * t1[0]) + w2 * t2[0];
+      const float v = (w0 * t0[1] + w1 * t1[1]) + w2 * t2[1];
+      const float4 s = sample_bilinear_border(tex + tex_off[b], th, tw, u * 2.f - 1.f, v * 2.f - 1.f);
+      alb[0] = s.x; alb[1] = s.y; alb[2] = s.z;
+    } else if (colors) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        alb[k] = (w0 * colors[3LL * (vb + v0) + k] + w1 * colors[3LL * (vb + v1) + k]) + w2 * colors[3LL * (vb + v2) + k];
+    }
+    float lit = 1.f, spec = 0.f;
+    if (shade) {
+      const float* p0 = verts + 3LL * (vb + v0);
+      const float* p1 = verts + 3LL * (vb + v1);
+      const float* p2 = verts + 3LL * (vb + v2);
+      float nx, ny, nz;
+      if (shade == 2) {                            // phong_shading: normalize(sum w_i n_i, eps 1e-6) of verts_normals_packed
+        const float* n0 = vnormals + 3LL * (vb + v0);
+        const float* n1 = vnormals + 3LL * (vb + v1);
+        const float* n2 = vnormals + 3LL * (vb + v2);
+        nx = (w0 * n0[0] + w1 * n1[0]) + w2 * n2[0];
+        ny = (w0 * n0[1] + w1 * n1[1]) + w2 * n2[1];
+        nz = (w0 * n0[2] + w1 * n1[2]) + w2 * n2[2];
+        const float nn = fmaxf(sqrtf((nx * nx + ny * ny) + nz * nz), 1e-6f);
+        nx = nx / nn; ny = ny / nn; nz = nz / nn;
+      } else {                                     // raster_resolve_kernel's flat face normal
+        const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
+        const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
+        nx = ay * bz - az * by; ny = az * bx - ax * bz; nz = ax * by - ay * bx;
+        const float nn = rsqrtf(fmaxf(nx * nx + ny * ny + nz * nz, 1e-30f));
+        nx *= nn; ny *= nn; nz *= nn;
+      }
+      const float qx = (w0 * p0[0] + w1 * p1[0]) + w2 * p2[0], qy = (w0 * p0[1] + w1 * p1[1]) + w2 * p2[1],
+                  qz = (w0 * p0[2] + w1 * p1[2]) + w2 * p2[2];
+      float lx = 1.f - qx, ly = 1.f - qy, lz = -1.f - qz;   // point light at (1, 1, -1), object space
+      float cosv;
+      if (shade == 2) {                            // diffuse(): relu(n . normalize(l, eps 1e-6)), one-sided
+        const float ln = fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-6f);
+        lx = lx / ln; ly = ly / ln; lz = lz / ln;
+        cosv = fmaxf((nx * lx + ny * ly) + nz * lz, 0.f);
+      } else {
+        const float ln = rsqrtf(fmaxf(lx * lx + ly * ly + lz * lz, 1e-30f));
+        cosv = fabsf((nx * lx + ny * ly + nz * lz) * ln);
+      }
+      lit = 0.5f + 0.3f * cosv;                    // ambient 0.5 + diffuse 0.3 (PointLights defaults, Materials white)
+      spec = 0.2f;                                 // specular 0.2 * pow(., shininess = 0) = 0.2 everywhere
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) col[k] = alb[k] * lit + spec;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k * P] = col[k];
+  o += 3 * P;
+  if (!attr || C <= 0) return;
+  const float* a0 = attr + attr_off[b] + static_cast<long long>(v0) * C;
+  const float* a1 = attr + attr_off[b] + static_cast<long long>(v1) * C;
+  const float* a2 = attr + attr_off[b] + static_cast<long long>(v2) * C;
+  int c = 0;
+  if ((C & 3) == 0 && (reinterpret_cast<uintptr_t>(attr) & 15) == 0 && (attr_off[b] & 3) == 0) {
+    for (; c < C; c += 4) {
+      float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (hit) {
+        const float4 q0 = *reinterpret_cast<const float4*>(a0 + c), q1 = *reinterpret_cast<const float4*>(a1 + c),
+                     q2 = *reinterpret_cast<const float4*>(a2 + c);
+        r = make_float4(w0 * q0.x + w1 * q1.x + w2 * q2.x, w0 * q0.y + w1 * q1.y + w2 * q2.y,
+                        w0 * q0.z + w1 * q1.z + w2 * q2.z, w0 * q0.w + w1 * q1.w + w2 * q2.w);
+      }
+      o[(c + 0) * P] = r.x; o[(c + 1) * P] = r.y; o[(c + 2) * P] = r.z; o[(c + 3) * P] = r.w;
+    }
+  }
+  for (; c < C; ++c) o[c * P] = hit ? w0 * a0[c] + w1 * a1[c] + w2 * a2[c] : 0.f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -245,6 +394,31 @@ int rnnpose_raster_resolve_f32(const float* verts, const int* faces, const int* 
                      face_off, T, K, H, W, near, pixel_center, perspective_correct,
                      static_cast<const unsigned long long*>(workspace), attr, attr_off, C, colors, with_color ? 3 : 0, shade,
                      empty_depth, out_attr, out_zbuf, out_vdepth);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_raster_resolve_tex_f32(const float* verts, const int* faces, const int* vert_off, const int* face_off, const float* T,
+                                   const float* K, int B, int H, int W, float near, float pixel_center, int perspective_correct,
+                                   const void* workspace, const float* attr, const long long* attr_off, int C,
+                                   const float* colors, const float* uvs, const int* face_uvs, const int* uv_off, const float* tex,
+                                   const long long* tex_off, const int* tex_hw, const float* vnormals, int shade,
+                                   float empty_depth, float* out_attr, float* out_zbuf, float* out_vdepth,
+                                   rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_raster_resolve_tex_f32";
+  RP_REQUIRE(verts && faces && vert_off && face_off && T && K && workspace, fn, "null pointer");
+  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && C >= 0, fn, "bad size");
+  RP_REQUIRE(shade >= 0 && shade <= 2, fn, "shade must be 0 (none), 1 (flat) or 2 (phong)");
+  RP_REQUIRE(!(attr && C > 0) || attr_off, fn, "attr needs attr_off");
+  RP_REQUIRE(!tex || (uvs && face_uvs && uv_off && tex_off && tex_hw), fn, "a texture needs uvs, face_uvs, uv_off, tex_off, tex_hw");
+  RP_REQUIRE(!tex || (reinterpret_cast<uintptr_t>(tex) & 15) == 0, fn, "texels must be 16-byte aligned (RGBA fp32)");
+  RP_REQUIRE(shade != 2 || vnormals, fn, "phong shading needs vnormals");
+  RP_REQUIRE(out_attr || out_zbuf || out_vdepth, fn, "nothing to write");
+  const long long P = static_cast<long long>(H) * W;
+  hipLaunchKernelGGL(raster_resolve_tex_kernel, dim3(rp::cdiv(P, 256), B), dim3(256), 0, rp::as_stream(stream), verts, faces,
+                     vert_off, face_off, T, K, H, W, near, pixel_center, perspective_correct,
+                     static_cast<const unsigned long long*>(workspace), attr, attr_off, C, colors, uvs, face_uvs, uv_off,
+                     reinterpret_cast<const float4*>(tex), tex_off, tex_hw, vnormals, shade, empty_depth, out_attr, out_zbuf,
+                     out_vdepth);
   return rp::check_launch(fn);
 }
 

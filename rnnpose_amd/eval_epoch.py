@@ -39,6 +39,9 @@ class ClassModel:
     geofea_3d: torch.Tensor      # (1,P,32) geometric descriptors of the vertices
     diameter: float
     eval_points: np.ndarray = None   # model points of the metric (defaults to verts)
+    verts_uvs: np.ndarray = None     # (U,2) texture coordinates of a textured model (mesh_io.load_obj), else None
+    faces_uvs: np.ndarray = None     # (F,3) int32 uv rows of each face
+    texture: np.ndarray = None       # (Ht,Wt,3) float32 in [0,1], the class's texture map
 
 
 @dataclass
@@ -123,8 +126,11 @@ class HipEpoch:
         from .rasterizer import MeshRenderer
         self.models = models
         self.device = torch.device(device)
-        self.renderer = MeshRenderer({n: dict(verts=m.verts, faces=m.faces, colors=m.colors) for n, m in models.items()},
-                                     device=device)
+        # textured models render as the reference's SoftPhongShader does; without one, the flat vertex-colour path as before
+        shading = "phong" if any(m.texture is not None for m in models.values()) else "flat"
+        self.renderer = MeshRenderer({n: dict(verts=m.verts, faces=m.faces, colors=m.colors, verts_uvs=m.verts_uvs,
+                                              faces_uvs=m.faces_uvs, texture=m.texture) for n, m in models.items()},
+                                     device=device, shading=shading)
         self.cfg = cfg if cfg is not None else default_config()
         self.refiner = refiner if refiner is not None else PoseRefiner(self.cfg, renderer=self.renderer).to(self.device).eval()
         self.symmetric = tuple(symmetric)

@@ -10,9 +10,19 @@ iteration stays on the GPU without PyTorch3D:
         -> ([shaded colour (3) |] interpolated vertex attributes (C), depth (-1 = empty))
     renderer.render_depth(model_names, T=, K=, render_image_size=, near=, far=)  nearest-vertex depth    (:327-367)
 
+Textured meshes (DiffRender.render_mesh, :104-120 and :201-242: `load_objs_as_meshes` + TexturesUV + SoftPhongShader):
+
+    renderer = MeshRenderer.from_obj({"cat": "models/cat/textured.obj"}, shading="phong")    # DiffRendererWrapper + cls2idx
+    renderer = MeshRenderer({"cat": dict(verts=, faces=, verts_uvs=, faces_uvs=, texture=)}, shading="phong")
+
+With render_tex=True the first three channels are then the texture sampled at the interpolated UV (grid_sample semantics of
+TexturesUV.sample_textures) and Phong-shaded per pixel with interpolated vertex normals (csrc/raster.hip,
+rnnpose_raster_resolve_tex_f32); a batch without a textured mesh under shading="flat" keeps the vertex-colour entry point.
+
 Kernels: csrc/raster.hip (z-buffer by 64-bit atomicMin keys + per-pixel resolve) and csrc/zoom_crop.hip (vertex splat).
 PARITY UNPINNED against PyTorch3D (absent here): semantics documented in include/rnnpose_hip.h, checked against
-oracle/raster_oracle.py and by properties in tests/test_raster.py.  Mesh loading (.ply / .obj) is outside: pass arrays.
+oracle/raster_oracle.py and by properties in tests/test_raster.py; textures and Phong against tests/texture_ref.py (a CPU
+restatement of PyTorch3D's chain on torch's grid_sample).  Mesh files: .obj through rnnpose_amd.mesh_io (no .ply).
 """
 from __future__ import annotations
 
@@ -23,11 +33,31 @@ import torch
 
 from . import _lib, ops
 
+SHADINGS = ("flat", "phong")
+
+
+def vertex_normals(verts, faces):
+    """PyTorch3D's Meshes.verts_normals_packed on the CPU in fp32: the area-weighted sum of the face normals
+    (v2 - v1) x (v0 - v1) at each vertex, normalised with eps 1e-6."""
+    v = torch.as_tensor(np.asarray(verts, dtype=np.float32))
+    f = torch.as_tensor(np.asarray(faces, dtype=np.int64))
+    vf = v[f]
+    fn = torch.cross(vf[:, 2] - vf[:, 1], vf[:, 0] - vf[:, 1], dim=1)
+    n = torch.zeros_like(v)
+    for k in range(3):
+        n.index_add_(0, f[:, k], fn)
+    return torch.nn.functional.normalize(n, eps=1e-6, dim=1)
+
 
 class MeshRenderer:
     def __init__(self, meshes: dict, device="cuda", pixel_center: float = 0.5, shade: bool = True,
-                 depth_perspective_correct: bool = True):
-        """meshes: {class name: dict(verts (P,3) float, faces (F,3) int, colors (P,3) float in [0,1] or None)}.
+                 depth_perspective_correct: bool = True, shading: str = "flat"):
+        """meshes: {class name: dict(verts (P,3) float, faces (F,3) int, colors (P,3) float in [0,1] or None,
+        optional verts_uvs (U,2) float, faces_uvs (F,3) int (uv rows of each face) and texture (Ht,Wt,3) float in [0,1], row 0 =
+        the image's top row as read from the file)}.
+        shading: "flat" (the two-sided flat-normal terms) or "phong" (PyTorch3D's phong_shading: interpolated vertex normals,
+        one-sided); shade=False renders the albedo unshaded.  Textured meshes and shading="phong" render their colour through
+        the textured resolve, where a mesh without a texture has its own vertex colours as albedo, or white without them.
         depth_perspective_correct: barycentrics of render_depth's nearest-vertex choice.  PyTorch3D resolves
         RasterizationSettings.perspective_correct=None to True for the PerspectiveCameras the reference builds
         (geometry/diff_render_optim.py:327-367), so True is the default; False = screen-space barycentrics.
@@ -37,6 +67,9 @@ class MeshRenderer:
         self.device = torch.device(device)
         self.pixel_center = float(pixel_center)
         self.shade = bool(shade)
+        if shading not in SHADINGS:
+            raise ValueError(f"shading must be one of {SHADINGS}, got {shading!r}")
+        self.shading = shading
         self.names = list(meshes)
         vo, fo, verts, faces, cols = {}, {}, [], [], []
         nv = nf = 0
@@ -61,6 +94,75 @@ class MeshRenderer:
         self.faces = torch.cat(faces).contiguous().to(self.device)
         self.colors = torch.cat(cols).contiguous().to(self.device) if self.has_colors else None
         self._batches = {}
+        self._tex = self._texture_data(meshes)
+
+    def _texture_data(self, meshes):
+        """Device arrays of the textured resolve, or None when no mesh is textured and shading is "flat"."""
+        tex_in = {}
+        for n in self.names:
+            m = meshes[n]
+            uv, fuv, tx = m.get("verts_uvs"), m.get("faces_uvs"), m.get("texture")
+            if tx is None:
+                continue
+            if uv is None or fuv is None:
+                raise ValueError(f"mesh {n!r}: a texture needs verts_uvs and faces_uvs")
+            uv = np.asarray(uv, dtype=np.float32)
+            fuv = np.asarray(fuv, dtype=np.int32)
+            tx = np.asarray(tx, dtype=np.float32)
+            if uv.ndim != 2 or uv.shape[1] != 2 or fuv.shape != (self._fo[n][1], 3):
+                raise ValueError(f"mesh {n!r}: verts_uvs must be (U,2), faces_uvs (F,3) with the F of faces")
+            if fuv.size and (int(fuv.min()) < 0 or int(fuv.max()) >= uv.shape[0]):
+                raise ValueError(f"mesh {n!r}: faces_uvs indices out of range")
+            if tx.ndim != 3 or tx.shape[2] != 3 or tx.shape[0] < 1 or tx.shape[1] < 1:
+                raise ValueError(f"mesh {n!r}: texture must be (Ht,Wt,3)")
+            tex_in[n] = (uv, fuv, tx)
+        self.textured = {n: n in tex_in for n in self.names}
+        if not tex_in and self.shading == "flat":
+            return None
+        d = dict(uv_off={}, tex_off={}, tex_hw={})
+        uvs, fuvs, texels, alb = [], [], [], []
+        nu = nt = 0
+        for n in self.names:
+            nv, nf = self._vo[n][1], self._fo[n][1]
+            c = meshes[n].get("colors")
+            alb.append(np.ones((nv, 3), np.float32) if c is None else np.asarray(c, dtype=np.float32).reshape(-1, 3))
+            if alb[-1].shape[0] != nv:
+                raise ValueError(f"mesh {n!r}: colors must be (P,3) with the P of verts")
+            if n in tex_in:
+                uv, fuv, tx = tex_in[n]
+                rgba = np.zeros(tx.shape[:2] + (4,), np.float32)
+                rgba[..., :3] = tx[::-1]                      # stored flipped: the kernel samples TexturesUV's flip(map, H) directly
+                d["uv_off"][n], d["tex_off"][n], d["tex_hw"][n] = nu, nt, tx.shape[:2]
+                uvs.append(uv)
+                fuvs.append(fuv)
+                texels.append(rgba.reshape(-1, 4))
+                nu += uv.shape[0]
+                nt += rgba.shape[0] * rgba.shape[1]
+            else:
+                d["uv_off"][n], d["tex_off"][n], d["tex_hw"][n] = 0, 0, (0, 0)
+                fuvs.append(np.zeros((nf, 3), np.int32))
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.concatenate(a))).to(self.device)
+        d["albedo"] = dev(alb)
+        d["uvs"] = dev(uvs) if tex_in else None
+        d["face_uvs"] = dev(fuvs) if tex_in else None
+        d["texels"] = dev(texels) if tex_in else None
+        d["vnormals"] = None
+        if self.shading == "phong":
+            d["vnormals"] = torch.cat([vertex_normals(meshes[n]["verts"], meshes[n]["faces"]) for n in self.names]) \
+                .contiguous().to(self.device)
+        return d
+
+    @classmethod
+    def from_obj(cls, paths: dict, device="cuda", shading: str = "phong", **kw):
+        """{class name: path of a .obj} -> MeshRenderer (rnnpose_amd.mesh_io.load_obj: UVs and the first material's texture
+        map; meshes without one are white).  The drop-in for the reference's DiffRendererWrapper(obj_paths) + cls2idx."""
+        from .mesh_io import load_obj
+        meshes = {}
+        for n, p in paths.items():
+            m = load_obj(p)
+            meshes[n] = dict(verts=m["verts"], faces=m["faces"], colors=None, verts_uvs=m["verts_uvs"],
+                             faces_uvs=m["faces_uvs"], texture=m["texture"])
+        return cls(meshes, device=device, shading=shading, **kw)
 
     def _batch(self, model_names):
         key = tuple(model_names)
@@ -72,6 +174,11 @@ class MeshRenderer:
                        nverts=[self._vo[n][1] for n in key],
                        pc_off=i32(np.concatenate([[0], np.cumsum([self._vo[n][1] for n in key])])),
                        same=all(n == key[0] for n in key))
+            if self._tex is not None:
+                tx = self._tex
+                hit.update(uv_off=i32([tx["uv_off"][n] for n in key]), tex_hw=i32([tx["tex_hw"][n] for n in key]),
+                           tex_off=torch.tensor([tx["tex_off"][n] for n in key], dtype=torch.int64, device=self.device),
+                           any_tex=any(self.textured[n] for n in key))
             if len(self._batches) > 64:
                 self._batches.clear()
             self._batches[key] = hit
@@ -116,6 +223,21 @@ class MeshRenderer:
                     float(empty_depth), ops._ptr(out), ops._ptr(zb), ops._ptr(vd), ops._stream())
         return out, zb, vd
 
+    def _resolve_tex(self, bt, T, K, size, near, ws, attr, attr_off, Cc):
+        """The textured resolve of __call__(render_tex=True): (B, 3 + Cc, H, W) maps and (B,1,H,W) depth (-1 = empty)."""
+        B, (H, W) = T.shape[0], (int(size[0]), int(size[1]))
+        tx = self._tex
+        out = torch.empty(B, 3 + Cc, H, W, device=self.device, dtype=torch.float32)
+        zb = torch.empty(B, 1, H, W, device=self.device, dtype=torch.float32)
+        shade = 0 if not self.shade else (2 if self.shading == "phong" else 1)
+        ops._launch("rnnpose_raster_resolve_tex_f32", ops._ptr(self.verts), ops._ptr(self.faces), ops._ptr(bt["vert_off"]),
+                    ops._ptr(bt["face_off"]), ops._ptr(T), ops._ptr(K), B, H, W, float(near), self.pixel_center, 1,
+                    ops._ptr(ws), ops._ptr(attr), ops._ptr(attr_off), Cc, ops._ptr(tx["albedo"]), ops._ptr(tx["uvs"]),
+                    ops._ptr(tx["face_uvs"]),
+                    ops._ptr(bt["uv_off"]), ops._ptr(tx["texels"]), ops._ptr(bt["tex_off"]), ops._ptr(bt["tex_hw"]),
+                    ops._ptr(tx["vnormals"]), shade, -1.0, ops._ptr(out), ops._ptr(zb), C.c_void_p(0), ops._stream())
+        return out, zb
+
     def render_depth(self, model_names, T, K, render_image_size, near=0.1, far=6):
         """(B,1,h,w): camera z of the nearest vertex of the visible face, 0 where empty (diff_render_optim.py:327-367)."""
         bt = self._batch(model_names)
@@ -147,6 +269,8 @@ class MeshRenderer:
                 raise ValueError(f"vert_attribute has {have} rows for image {b}, its model has {nverts} vertices")
         attr_off = torch.tensor(offs, dtype=torch.int64, device=self.device)
         ws = self._raster(bt, T, K, render_image_size, near, perspective=True)
+        if render_tex and self._tex is not None and (bt["any_tex"] or self.shading == "phong"):
+            return self._resolve_tex(bt, T, K, render_image_size, near, ws, attr, attr_off, Cc)
         out, zb, _ = self._resolve(bt, T, K, render_image_size, near, True, ws, attr=attr, attr_off=attr_off, Cc=Cc,
                                    with_color=bool(render_tex), want_zbuf=True, empty_depth=-1.0)
         return out, zb
