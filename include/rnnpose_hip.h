@@ -578,6 +578,13 @@ int rnnpose_zoom_crop_params_f32(const int* bbox, const float* K, const float* T
                                  float margin_ratio, float* theta, float* K_crop, rnnpose_stream_t stream);
 int rnnpose_zoom_crop_f32(const float* in, const float* theta, int B, int C, int H, int W, int crop_h, int crop_w, float* out,
                           float* grid_out, rnnpose_stream_t stream);
+/* zoom_crop_indexed: the same crop from SHARED sources (several objects of one camera frame): in (S,C,H,W), src_index (B) device
+ *   int32 with 0 <= src_index[b] < S; out[b] = grid_sample(in[src_index[b]], affine_grid(theta[b])), the arithmetic of
+ *   rnnpose_zoom_crop_f32 operation for operation (src_index = 0..B-1 gives its output bit for bit).  THE CALLER checks the index
+ *   range on the host before the launch (the entries are device memory; rnnpose_amd.ops.zoom_crop does); a crop whose index is
+ *   outside [0,S) reads nothing: its out is zeros (its grid_out is not written) and the call still returns 0. */
+int rnnpose_zoom_crop_indexed_f32(const float* in, const int* src_index, const float* theta, int S, int B, int C, int H, int W,
+                                  int crop_h, int crop_w, float* out, float* grid_out, rnnpose_stream_t stream);
 
 /* ---- f4 (second half): triangle-mesh rasteriser of the render hand-off ------------------------------------------------
  *      geometry/diff_render_optim.py:283-367 (DiffRender.forward / render_depth on PyTorch3D's MeshRasterizer,

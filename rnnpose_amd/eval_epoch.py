@@ -53,6 +53,7 @@ class EvalItem:
     pose_init: np.ndarray        # (4,4) initial pose (PoseCNN / PVNet in the reference)
     pose_gt: np.ndarray          # (4,4)
     geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image (None: HipEpoch(desc2d=...) computes them)
+    frame_id: int | None = None  # camera frame the object was seen in: items of one frame share `image` / `geofea_2d` (None: its own)
 
 
 class PackedEpochMetrics:
@@ -84,6 +85,24 @@ def class_batches(items, indices, unique, batch_size):
     return out
 
 
+def frame_batches(items, indices, unique, batch_size):
+    """The shard's samples as batches of ONE CAMERA FRAME each, whatever the classes of its objects, in shard order:
+    consecutive shard items with the same non-None `frame_id` share a batch (a frame with more than batch_size objects is
+    split); items without a frame id batch as class_batches does.  -> [(None | class, [item index], [unique flag])]: None
+    marks a frame batch (mixed classes, one shared image)."""
+    out, keys = [], []
+    for i, u in zip(indices, unique):
+        f = items[i].frame_id
+        key = ("frame", f) if f is not None else ("class", items[i].class_name)
+        if out and keys[-1] == key and len(out[-1][1]) < batch_size:
+            out[-1][1].append(i)
+            out[-1][2].append(u)
+        else:
+            out.append((None if f is not None else items[i].class_name, [i], [u]))
+            keys.append(key)
+    return out
+
+
 def flags_from_metrics(m, diameter, symmetric):
     """(B,5) [ADD, ADD-S, proj2d px, translation cm, rotation deg] -> (B,5) 0/1 flags in METRICS order
     (utils/eval_metric.py:102-192: ADD(-S) < 10 % / 2 % / 5 % of the diameter, proj2d < 5 px, 5 cm 5 deg)."""
@@ -93,26 +112,36 @@ def flags_from_metrics(m, diameter, symmetric):
                      (m[:, 3] < 5.0) & (m[:, 4] < 5.0)], 1).astype(np.float64)
 
 
-def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8, symmetric=(), reduce_device=None):
+def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8, symmetric=(), reduce_device=None, group="class"):
     """items: list[EvalItem]; models: {class: ClassModel};
     refine_fn(class_name, [EvalItem]) -> (B,4,4) refined poses (numpy or tensor): one PoseRefiner call per batch;
     metric_fn(class_name, pose_pred (B,4,4), pose_gt (B,4,4)) -> (B,5) [ADD, ADD-S, proj2d, t cm, r deg].
+    group="class": batches of one class (the reference's restriction).  group="frame": frame_batches -- the objects of one
+    camera frame in one batch whatever their classes; refine_fn is then called as refine_fn(None, batch) (HipEpoch.refine_frame
+    behind `lambda _, batch: epoch.refine_frame(batch)`) and every item's metrics are booked under its own class, with that
+    class's diameter and symmetry.
     -> {"init": {cls: {metric: mean, "n": count}}, "refined": {...}} identical on every rank (wrap-around duplicates of the
     sampler are excluded from the sums)."""
+    if group not in ("class", "frame"):
+        raise ValueError(f"group must be 'class' or 'frame', got {group!r}")
     classes = sorted(models)
     idx, uniq = D.shard_indices(len(items), rank, world)
     acc = PackedEpochMetrics(classes)
-    for cls, ids, us in class_batches(items, idx, uniq, batch_size):
+    batches = class_batches(items, idx, uniq, batch_size) if group == "class" else frame_batches(items, idx, uniq, batch_size)
+    for cls, ids, us in batches:
         batch = [items[i] for i in ids]
         gt = np.stack([it.pose_gt for it in batch]).astype(np.float32)
         init = np.stack([it.pose_init for it in batch]).astype(np.float32)
-        pred = refine_fn(cls, batch)
+        pred = refine_fn(cls if group == "class" else None, batch)
         pred = pred.detach().cpu().numpy() if torch.is_tensor(pred) else np.asarray(pred)
-        sym = cls in symmetric
-        for which, poses in ((acc.init, init), (acc.refined, pred.reshape(-1, 4, 4))):
-            fl = flags_from_metrics(metric_fn(cls, poses, gt), models[cls].diameter, sym)
-            for row, u in zip(fl, us):
-                which.update(cls, dict(zip(METRICS, row)), unique=u)
+        pred = pred.reshape(-1, 4, 4)
+        for c in sorted({it.class_name for it in batch}):           # one class in a class batch; per-item classes in a frame batch
+            rows = [j for j, it in enumerate(batch) if it.class_name == c]
+            sym = c in symmetric
+            for which, poses in ((acc.init, init), (acc.refined, pred)):
+                fl = flags_from_metrics(metric_fn(c, poses[rows], gt[rows]), models[c].diameter, sym)
+                for row, j in zip(fl, rows):
+                    which.update(c, dict(zip(METRICS, row)), unique=us[j])
     return acc.reduce(device=reduce_device)
 
 
@@ -137,6 +166,7 @@ class HipEpoch:
         # desc2d: a descriptor2d.SuperPoint2D -- items without geofea_2d get theirs from the batch image on the device, as
         # model/RNNPose.py:162 computes them (HybridNet.py:97 keeps the descriptors only)
         self.desc2d = desc2d
+        self._frame_tables = None         # refine_frame: resident or per-object, decided on its first call
         self.evaluators = {n: LineMODEvaluator(n, m.eval_points if m.eval_points is not None else m.verts, m.diameter,
                                                device=device) for n, m in models.items()}
         for n, e in self.evaluators.items():
@@ -164,6 +194,48 @@ class HipEpoch:
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=m.fea_3d.to(dev), Tj_gt=SE3Sequence(matrix=Tg[:, None]),
                            obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2)
+        return out["Ti_pred"].G.reshape(-1, 4, 4)
+
+    def _resident_tables(self):
+        """On the first refine_frame: lay every class's [context | descriptor] table out once in the refiner's renderer
+        (MeshRenderer.set_vertex_attributes).  False when that renderer keeps no tables or the classes' channel counts differ:
+        refine_frame then passes one table per object."""
+        if self._frame_tables is None:
+            ren = getattr(self.refiner.renderer, "renderer", None)
+            tables = {n: torch.cat([m.fea_3d, m.geofea_3d], -1)[0] for n, m in self.models.items()}
+            self._frame_tables = hasattr(ren, "set_vertex_attributes") and len({t.shape[1] for t in tables.values()}) == 1
+            if self._frame_tables:
+                ren.set_vertex_attributes(tables)
+        return self._frame_tables
+
+    def refine_frame(self, batch):
+        """The objects of one or several camera frames, of any classes, in ONE PoseRefiner call: the image and its descriptor
+        map are held once per distinct frame (items with the same non-None frame_id; an item without one is its own frame),
+        `SuperPoint2D.descriptors` runs once per frame that carries no geofea_2d, and every object crops its frame through
+        image_index.  -> (B,4,4) refined poses in batch order."""
+        from .transformation import SE3Sequence
+        dev = self.device
+        src, index = {}, []
+        for j, it in enumerate(batch):
+            key = ("frame", it.frame_id) if it.frame_id is not None else ("item", j)
+            index.append(src.setdefault(key, (len(src), it))[0])
+        firsts = [it for _, it in sorted(src.values(), key=lambda v: v[0])]
+        image = torch.stack([it.image for it in firsts]).to(dev)
+        missing = [s for s, it in enumerate(firsts) if it.geofea_2d is None]
+        if missing and self.desc2d is None:
+            raise ValueError("items without geofea_2d need HipEpoch(desc2d=SuperPoint2D(...))")
+        fresh = iter(self.desc2d.descriptors(image[missing].float().contiguous())) if missing else iter(())
+        g2 = torch.stack([next(fresh) if it.geofea_2d is None else it.geofea_2d.to(dev) for it in firsts])
+        K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
+        T0 = torch.as_tensor(np.stack([it.pose_init for it in batch]).astype(np.float32)).to(dev)
+        Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
+        names = [it.class_name for it in batch]
+        fea = geo = None                                             # = the renderer's resident tables
+        if not self._resident_tables():
+            fea = [self.models[n].fea_3d.to(dev)[0] for n in names]
+            geo = [self.models[n].geofea_3d.to(dev)[0] for n in names]
+        out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=fea, Tj_gt=SE3Sequence(matrix=Tg[:, None]),
+                           obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index)
         return out["Ti_pred"].G.reshape(-1, 4, 4)
 
     def metrics(self, cls, pose_pred, pose_gt):
@@ -252,4 +324,53 @@ def synthetic_dataset(models, n_items, image_size=(480, 640), seed=0, pose_sigma
             for j, i in enumerate(sub_ids):
                 items[i].image = (out[j, :3] * 255.0).cpu()
                 items[i].geofea_2d = out[j, 3:].cpu()
+    return items
+
+
+def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640), seed=0, pose_sigma=(0.05, 0.01), renderer=None,
+                     device="cuda"):
+    """n_frames camera frames with objects_per_frame objects each, of different classes (cycling through them), at separated
+    image positions and depths: every object is rendered at its ground-truth pose by `renderer` (MeshRenderer) and the frame is
+    composed by nearest depth in torch -- colour and rendered descriptors alike -- so nearer objects occlude farther ones.
+    Every object becomes an EvalItem that SHARES the frame's image and geofea_2d tensors and carries its frame_id; items of a
+    frame are consecutive.  renderer=None (CPU): hash noise per frame instead of a render."""
+    from . import synthetic as syn
+    from .evaluator import LINEMOD_K
+    H, W = image_size
+    names = sorted(models)
+    K = LINEMOD_K.copy()
+    K[0, 2], K[1, 2] = W / 2.0, H / 2.0
+    cols = int(np.ceil(np.sqrt(objects_per_frame)))
+    rows = -(-objects_per_frame // cols)
+    # grid cells of 0.8 x the image at 0.8 m, shrunk towards the centre so that the objects stay inside the frame
+    dx, dy = 0.8 * W / K[0, 0] * 0.8 / max(cols, 1), 0.8 * H / K[1, 1] * 0.8 / max(rows, 1)
+    items = []
+    for f in range(n_frames):
+        frame = []
+        for j in range(objects_per_frame):
+            cls = names[(f + j) % len(names)]
+            i = f * objects_per_frame + j
+            g = syn.se3_exp_np(syn.normal(f"sgt{i}", (1, 6), seed, std=0.6))[0]
+            cell = np.array([(j % cols - (cols - 1) / 2.0) * dx, (j // cols - (rows - 1) / 2.0) * dy, 0.8 + 0.06 * ((j * 5) % 7) / 7.0])
+            g[:3, 3] = syn.uniform(f"st{i}", (3,), seed, -0.1, 0.1) * np.array([dx, dy, 0.05]) + cell      # jitter within the cell
+            xi = syn.normal(f"sxi{i}", (1, 6), seed)[0] * np.array([pose_sigma[1]] * 3 + [pose_sigma[0]] * 3)
+            init = syn.se3_exp_np(xi[None])[0] @ g
+            frame.append(EvalItem(cls, None, K.copy(), init.astype(np.float32), g.astype(np.float32), None, frame_id=f))
+        if renderer is None:
+            image = torch.from_numpy(syn.uniform(f"simg{f}", (3, H, W), seed) * 255.0)
+            g2 = torch.from_numpy(syn.normal(f"sg2{f}", (32, H, W), seed))
+        else:
+            dev = torch.device(device)
+            Tg = torch.as_tensor(np.stack([it.pose_gt for it in frame])).to(dev)
+            Kt = torch.as_tensor(np.stack([it.K for it in frame])).to(dev)
+            out, depth = renderer([it.class_name for it in frame], [models[it.class_name].geofea_3d[0].to(dev) for it in frame],
+                                  T=Tg, K=Kt, render_image_size=(H, W), render_tex=True)
+            z = torch.where(depth > 0, depth, torch.full_like(depth, float("inf")))          # (n,1,H,W); -1 = empty
+            near = z.argmin(0, keepdim=True)                                                 # nearest object per pixel
+            comp = torch.gather(out, 0, near.expand(1, out.shape[1], H, W))[0]
+            comp = comp * torch.isfinite(z.min(0).values).to(comp.dtype)                     # background stays 0
+            image, g2 = (comp[:3] * 255.0).cpu(), comp[3:].cpu()
+        for it in frame:
+            it.image, it.geofea_2d = image, g2
+        items += frame
     return items

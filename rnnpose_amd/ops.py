@@ -1534,14 +1534,58 @@ def zoom_crop_params(bbox, K, T, image_size, crop_size, margin_ratio=0.4):
     return theta, K_crop
 
 
-def zoom_crop(x, theta, crop_size, want_grid=False):
+class SourceIndex:
+    """Which source image every crop of a batch reads (`zoom_crop(..., src_index=)`), checked ON THE HOST once: index (B,) with
+    0 <= index[b] < S.  Holds the device copy the kernel reads.
+    Build it once per batch (rnnpose_amd.PoseRefiner does, per forward) and every crop of that batch launches without a
+    device->host copy; a plain tensor / list passed as src_index is checked -- and copied -- on every call."""
+
+    def __init__(self, index, S, device):
+        if isinstance(index, torch.Tensor):
+            if index.dtype.is_floating_point or index.dtype == torch.bool or index.dim() != 1:
+                raise ValueError("src_index must be a 1-D integer tensor")
+            host = [int(v) for v in index.detach().cpu().tolist()]
+        else:
+            host = [int(v) for v in index]
+        self.S = int(S)
+        bad = [v for v in host if not 0 <= v < self.S]
+        if not host or bad:
+            raise ValueError(f"src_index entries must lie in [0, {self.S}) and there must be at least one: got {bad[:4] or host}")
+        self.host = tuple(host)
+        self.dev = torch.tensor(host, dtype=torch.int32, device=device)
+
+    def __len__(self):
+        return len(self.host)
+
+    def gather(self, x):
+        """x (S, ...) -> (B, ...) = x[index] (torch indexing; for the few callers that need the copy)."""
+        return x[self.dev.long()]
+
+
+def zoom_crop(x, theta, crop_size, want_grid=False, src_index=None):
     """F.grid_sample(x, F.affine_grid(theta, (B,C,*crop_size))) fused (bilinear, zeros, align_corners=False).
-    x (B,C,H,W) or None (grid only) -> out (B,C,hc,wc) [, grid (B,hc,wc,2)]."""
+    x (B,C,H,W) or None (grid only) -> out (B,C,hc,wc) [, grid (B,hc,wc,2)].
+    src_index (None = crop b reads x[b]): a SourceIndex, or B integers (tensor / sequence) with 0 <= src_index[b] < S for
+    x (S,C,H,W): crop b reads x[src_index[b]] -- one image shared by several crops (rnnpose_zoom_crop_indexed_f32).  Entries
+    outside [0, S) raise ValueError here, on the host; nothing is launched."""
     theta = _chk(theta, "theta")
     B = theta.shape[0]
     hc, wc = int(crop_size[0]), int(crop_size[1])
     out = None
     C_, H, W = 0, 1, 1
+    if src_index is not None:
+        if x is None:
+            raise ValueError("src_index needs a source tensor x")
+        x = _chk(x, "x")
+        S, C_, H, W = x.shape
+        if not isinstance(src_index, SourceIndex):
+            src_index = SourceIndex(src_index, S, theta.device)
+        if src_index.S != S or len(src_index) != B:
+            raise ValueError(f"src_index covers {len(src_index)} crops of {src_index.S} sources; theta has {B} crops, x {S} sources")
+        out = torch.empty(B, C_, hc, wc, device=theta.device, dtype=F32)
+        grid = torch.empty(B, hc, wc, 2, device=theta.device, dtype=F32) if want_grid else None
+        _launch("rnnpose_zoom_crop_indexed_f32", _ptr(x), _ptr(src_index.dev), _ptr(theta), S, B, C_, H, W, hc, wc, _ptr(out), _ptr(grid), _stream())
+        return (out, grid) if want_grid else out
     if x is not None:
         x = _chk(x, "x")
         _, C_, H, W = x.shape

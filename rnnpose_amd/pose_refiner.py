@@ -57,6 +57,25 @@ class SyntheticRenderer:
         return self.views
 
 
+class SynImgTail:
+    """The four maps the reference appends to `syn_img` (model/PoseRefiner.py:374), of the last outer iteration, (B,3,h,w) each:
+    image_crop, cfea_crop[:, :3] * 10, geofea1[:, :3], geofea2_crop[:, :3].  A read-only sequence that forms an entry when it is
+    read: forward() itself launches and allocates nothing for a diagnostic few callers look at."""
+
+    def __init__(self, views):
+        self._get = (lambda: views["image_crop"], lambda: views["cfea"][:, :3] * 10, lambda: views["geofea1"][:, :3],
+                     lambda: views["geofea2_crop"][:, :3])
+
+    def __len__(self):
+        return 4
+
+    def __getitem__(self, i):
+        return self._get[i]()
+
+    def __iter__(self):
+        return (g() for g in self._get)
+
+
 class PoseRefiner(nn.Module):
     def __init__(self, cfg=None, reuse=False, schedule=None, use_regressor=True, is_calibrated=True,
                  bn_is_training=False, is_training=True, renderer=None, fused=True,
@@ -397,9 +416,23 @@ class PoseRefiner(nn.Module):
             eng.state_restore(snap)
 
     @torch.no_grad()
-    def forward(self, image, Ts, intrinsics, fea_3d=None, Tj_gt=None, obj_cls=None, geofea_3d=None, geofea_2d=None):
-        """image (B,3,H0,W0); Ts SE3Sequence (B,1,4,4); intrinsics (B,3,3) -> dict (PoseRefiner.py:366-376)."""
+    def forward(self, image, Ts, intrinsics, fea_3d=None, Tj_gt=None, obj_cls=None, geofea_3d=None, geofea_2d=None,
+                image_index=None):
+        """image (B,3,H0,W0); Ts SE3Sequence (B,1,4,4); intrinsics (B,3,3) -> dict (PoseRefiner.py:366-376).
+        Several objects of one camera frame (mixed classes): image (S,3,H0,W0) and geofea_2d (S,32,H0,W0) with S <= B sources
+        and image_index (B,) integers naming the source of every object; obj_cls names every object's class; fea_3d /
+        geofea_3d are one tensor (one class for the whole batch), a list of B (P_b, C) tables, or None when the renderer
+        holds resident tables (MeshRenderer.set_vertex_attributes).  image_index=None: S == B, object b crops image b.
+        Everything downstream of the render hand-off sees (B, ...) views and is per image, so the batch halves, the
+        graph caches and the inner loop are the ones of a single-class batch of the same size."""
         self._clear()
+        views_kw = {}
+        prep = getattr(self.renderer, "prepare_inputs", None)
+        if prep is not None:          # host-side checks first: a batch the render hand-off cannot serve launches nothing
+            image_index = prep(Ts.G.shape[0], obj_cls=obj_cls, image=image, fea_3d=fea_3d, geofea_3d=geofea_3d,
+                               geofea_2d=geofea_2d, image_index=image_index)
+        if image_index is not None:
+            views_kw["image_index"] = image_index
         if image is not None and image.is_cuda or intrinsics.is_cuda:
             from .streams import reserve
             reserve(intrinsics.device)        # bind the concurrent streams to distinct hardware queues before anything else
@@ -439,7 +472,7 @@ class PoseRefiner(nn.Module):
             if self.legacy and self.literal_legacy_pose and not fused_pose:
                 Tij = Ti * Ti.inv()
             views = self.renderer.render_views(Ti.matrix().squeeze(1), intrinsics, obj_cls=obj_cls, image=image,
-                                               fea_3d=fea_3d, geofea_3d=geofea_3d, geofea_2d=geofea_2d)
+                                               fea_3d=fea_3d, geofea_3d=geofea_3d, geofea_2d=geofea_2d, **views_kw)
             syn_depth = views["syn_depth"]
             intrinsics_crop = views["intrinsics_crop"]
             cfea_crop = views["cfea"]
@@ -504,6 +537,7 @@ class PoseRefiner(nn.Module):
             "weight": corr_weight.permute(0, 1, 4, 2, 3),
             "syn_depth": syn_depths,
             "syn_img": syn_imgs,
+            "syn_img_tail": SynImgTail(views),
             "Tij_gt": Tij_gt,
             # sticky count of activation quads the fp16x3 split had to clamp so far (device tensor, no host sync): nonzero
             # means some value left the +-8188 range the fp32 reference would have handled

@@ -94,6 +94,7 @@ class MeshRenderer:
         self.faces = torch.cat(faces).contiguous().to(self.device)
         self.colors = torch.cat(cols).contiguous().to(self.device) if self.has_colors else None
         self._batches = {}
+        self._attr = None                 # set_vertex_attributes(): resident per-class attribute tables
         self._tex = self._texture_data(meshes)
 
     def _texture_data(self, meshes):
@@ -163,6 +164,47 @@ class MeshRenderer:
             meshes[n] = dict(verts=m["verts"], faces=m["faces"], colors=None, verts_uvs=m["verts_uvs"],
                              faces_uvs=m["faces_uvs"], texture=m["texture"])
         return cls(meshes, device=device, shading=shading, **kw)
+
+    def set_vertex_attributes(self, tables: dict):
+        """Lay the per-vertex attribute tables {class name: (P, C) or (1, P, C) tensor} out ONCE in one device buffer;
+        `renderer(model_names, None, ...)` then renders every image with the table of its class, without the per-call
+        concatenation a list of tables costs.  All tables share C and have at least as many rows as their mesh has
+        vertices; classes left out keep no table (asking for one raises ValueError).  Replaces earlier tables."""
+        rows, off, n, Cc = [], {}, 0, None
+        for name, t in tables.items():
+            if name not in self._vo:
+                raise ValueError(f"set_vertex_attributes: {name!r} is not a mesh of this renderer")
+            t = t.reshape(-1, t.shape[-1]) if t.dim() == 3 and t.shape[0] == 1 else t
+            if t.dim() != 2:
+                raise ValueError(f"set_vertex_attributes: table of {name!r} must be (P, C), got {tuple(t.shape)}")
+            if Cc is not None and t.shape[1] != Cc:
+                raise ValueError(f"set_vertex_attributes: tables of different C ({Cc} and {t.shape[1]} for {name!r})")
+            if t.shape[0] < self._vo[name][1]:
+                raise ValueError(f"set_vertex_attributes: {name!r} has {t.shape[0]} rows, its mesh {self._vo[name][1]} vertices")
+            Cc = int(t.shape[1])
+            off[name] = n
+            n += int(t.shape[0]) * Cc
+            rows.append(t)
+        if not rows:
+            raise ValueError("set_vertex_attributes: no table given")
+        self._attr = dict(buf=torch.cat([r.to(self.device).float() for r in rows]).contiguous(), off=off, C=Cc)
+        for bt in self._batches.values():
+            bt.pop("attr_off", None)
+
+    def _resident_attr(self, bt, model_names):
+        """(attr, attr_off, C) of a batch rendered from the resident tables; attr_off is cached with the batch."""
+        at = self._attr
+        if at is None:
+            raise ValueError("vert_attribute=None needs resident tables: call set_vertex_attributes() first")
+        if "attr_off" not in bt:
+            missing = sorted({n for n in model_names if n not in at["off"]})
+            if missing:
+                raise ValueError(f"no resident attribute table for {missing}")
+            bt["attr_off"] = torch.tensor([at["off"][n] for n in model_names], dtype=torch.int64, device=self.device)
+        return at["buf"], bt["attr_off"], at["C"]
+
+    def has_vertex_attributes(self, model_names):
+        return self._attr is not None and all(n in self._attr["off"] for n in model_names)
 
     def _batch(self, model_names):
         key = tuple(model_names)
@@ -246,14 +288,14 @@ class MeshRenderer:
         ws = self._raster(bt, T, K, render_image_size, near, perspective=pc)
         return self._resolve(bt, T, K, render_image_size, near, pc, ws, want_vdepth=True)[2]
 
-    def __call__(self, model_names, vert_attribute, T, K, render_image_size, near=0.1, far=6, render_tex=False):
-        """vert_attribute: (B or 1, P, C) per-vertex rows (or a list of (P_b, C)) -> (maps (B,[3+]C,h,w), depth (B,1,h,w), -1 = empty)."""
-        bt = self._batch(model_names)
-        T, K = self._tk(T, K)
-        B = T.shape[0]
+    def _explicit_attr(self, bt, vert_attribute, B):
         if isinstance(vert_attribute, (list, tuple)):
+            if len(vert_attribute) < B:
+                raise ValueError(f"vert_attribute lists {len(vert_attribute)} tables for {B} images")
             rows = [a.float().reshape(-1, a.shape[-1]) for a in vert_attribute]
             Cc = rows[0].shape[1]
+            if any(r.shape[1] != Cc for r in rows):
+                raise ValueError(f"vert_attribute tables of different C: {sorted({int(r.shape[1]) for r in rows})}")
             attr = torch.cat(rows).contiguous()
             offs = np.concatenate([[0], np.cumsum([r.shape[0] * Cc for r in rows])])[:B]
         else:
@@ -267,7 +309,20 @@ class MeshRenderer:
             have = (rows[b].shape[0] if isinstance(vert_attribute, (list, tuple)) else attr.shape[1])
             if have < nverts:
                 raise ValueError(f"vert_attribute has {have} rows for image {b}, its model has {nverts} vertices")
-        attr_off = torch.tensor(offs, dtype=torch.int64, device=self.device)
+        return attr, torch.tensor(offs, dtype=torch.int64, device=self.device), Cc
+
+    def __call__(self, model_names, vert_attribute=None, T=None, K=None, render_image_size=None, near=0.1, far=6, render_tex=False):
+        """vert_attribute: (B or 1, P, C) per-vertex rows, a list of (P_b, C), or None = the resident table of every image's
+        class (set_vertex_attributes) -> (maps (B,[3+]C,h,w), depth (B,1,h,w), -1 = empty)."""
+        if T is None or K is None or render_image_size is None:
+            raise TypeError("MeshRenderer() needs T, K and render_image_size")
+        bt = self._batch(model_names)
+        T, K = self._tk(T, K)
+        B = T.shape[0]
+        if vert_attribute is None:
+            attr, attr_off, Cc = self._resident_attr(bt, model_names)
+        else:
+            attr, attr_off, Cc = self._explicit_attr(bt, vert_attribute, B)
         ws = self._raster(bt, T, K, render_image_size, near, perspective=True)
         if render_tex and self._tex is not None and (bt["any_tex"] or self.shading == "phong"):
             return self._resolve_tex(bt, T, K, render_image_size, near, ws, attr, attr_off, Cc)

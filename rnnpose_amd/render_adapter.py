@@ -42,31 +42,103 @@ class RendererAdapter:
         self.margin_ratio = float(margin_ratio)
         self.near, self.far = near, far
 
+    def prepare_inputs(self, B, obj_cls=None, image=None, fea_3d=None, geofea_3d=None, geofea_2d=None, image_index=None):
+        """Host-side checks of one PoseRefiner.forward() call, before anything is launched (ValueError on a batch the
+        render hand-off cannot serve) -> the ops.SourceIndex of a batch that shares source images, or None.
+        image (S,3,H,W) / geofea_2d (S,32,H,W): S == B without image_index (crop b reads image b), else image_index (B,)
+        names the source of every object, 0 <= image_index[b] < S.  fea_3d / geofea_3d: one tensor for the whole batch, a
+        list of B per-image (P_b, C) tables, or None when the renderer holds a resident table for every class of obj_cls."""
+        from . import ops
+        r = self.renderer
+        names = getattr(r, "names", None)
+        if names is not None and obj_cls is not None:
+            unknown = sorted({str(n) for n in obj_cls if n not in names})
+            if unknown:
+                raise ValueError(f"unknown object class {unknown}: the renderer holds {sorted(names)}")
+        if obj_cls is not None and len(obj_cls) != B:
+            raise ValueError(f"obj_cls names {len(obj_cls)} objects, the poses {B}")
+        for name, t in (("fea_3d", fea_3d), ("geofea_3d", geofea_3d)):
+            if isinstance(t, (list, tuple)):
+                if len(t) != B:
+                    raise ValueError(f"{name} lists {len(t)} tables for {B} objects")
+                if len({int(a.shape[-1]) for a in t}) != 1:
+                    raise ValueError(f"{name}: tables of different C {sorted({int(a.shape[-1]) for a in t})}")
+        if fea_3d is None:
+            if geofea_3d is not None:
+                raise ValueError("geofea_3d without fea_3d: pass both, or neither to render from the resident tables")
+            has = getattr(r, "has_vertex_attributes", None)
+            if has is None or obj_cls is None or not has(obj_cls):
+                raise ValueError("fea_3d=None needs a renderer with a resident attribute table for every class of obj_cls "
+                                 "(MeshRenderer.set_vertex_attributes)")
+        S = None
+        for name, t in (("image", image), ("geofea_2d", geofea_2d)):
+            if t is None:
+                continue
+            if S is not None and t.shape[0] != S:
+                raise ValueError(f"image holds {S} sources, geofea_2d {t.shape[0]}")
+            S = int(t.shape[0])
+        if image_index is None:
+            if S is not None and S != B:
+                raise ValueError(f"{S} source images for {B} objects need image_index (which source each object crops from)")
+            return None
+        if S is None:
+            raise ValueError("image_index without an image")
+        if isinstance(image_index, ops.SourceIndex):
+            idx = image_index
+            if idx.S != S:
+                raise ValueError(f"image_index was built for {idx.S} sources, image holds {S}")
+        else:
+            idx = ops.SourceIndex(image_index, S, image.device)
+        if len(idx) != B:
+            raise ValueError(f"image_index names {len(idx)} objects, the poses {B}")
+        return idx
+
+    @staticmethod
+    def _per_image(t, b):
+        """Table b of a per-batch attribute argument: a list entry, row b of (B,P,C), or the one shared (1,P,C) / (P,C) table."""
+        if isinstance(t, (list, tuple)):
+            return t[b].reshape(-1, t[b].shape[-1])
+        return t.reshape(-1, t.shape[-1]) if t.dim() == 2 or t.shape[0] == 1 else t[b]
+
     @torch.no_grad()
-    def render_views(self, Ti, intrinsics, obj_cls=None, image=None, fea_3d=None, geofea_3d=None, geofea_2d=None):
-        """Ti (B,4,4) current absolute pose, intrinsics (B,3,3) of the full image -> views dict of one outer iteration."""
+    def render_views(self, Ti, intrinsics, obj_cls=None, image=None, fea_3d=None, geofea_3d=None, geofea_2d=None,
+                     image_index=None):
+        """Ti (B,4,4) current absolute pose, intrinsics (B,3,3) of the full image -> views dict of one outer iteration.
+        image_index (ops.SourceIndex or B integers; see prepare_inputs): object b crops image / geofea_2d [image_index[b]]."""
         r, zs = self.renderer, self.zoom_crop_size
         pc_depth = r.render_pointcloud(obj_cls, T=Ti, K=intrinsics, render_image_size=self.render_image_size)       # :253-254
         B = pc_depth.shape[0]
         # foreground mask = pc_depth > 0 (:259); window, grids and cropped intrinsics on the device (:145-218)
         _, K_crop, theta = zoom.gen_zoom_crop_grids(pc_depth, intrinsics, Ti, [B, 1, *zs], margin_ratio=self.margin_ratio,
                                                     want_grids=False)
-        fea_cat = torch.cat([fea_3d, geofea_3d], dim=-1) if geofea_3d is not None else fea_3d                        # :269-272
+        lists = isinstance(fea_3d, (list, tuple)) or isinstance(geofea_3d, (list, tuple))
+        if fea_3d is None:                       # resident tables of the renderer: [context | descriptor] channels per class
+            fea_cat, c3, cg = None, None, (geofea_2d.shape[1] if geofea_2d is not None else 0)
+        elif lists:                              # one (P_b, C) table per image: a mixed-class batch
+            c3 = self._per_image(fea_3d, 0).shape[-1]
+            cg = self._per_image(geofea_3d, 0).shape[-1] if geofea_3d is not None else 0
+            fea_cat = [self._per_image(fea_3d, b) if geofea_3d is None else
+                       torch.cat([self._per_image(fea_3d, b), self._per_image(geofea_3d, b)], dim=-1) for b in range(B)]
+        else:
+            c3, cg = fea_3d.shape[-1], (geofea_3d.shape[-1] if geofea_3d is not None else 0)
+            fea_cat = torch.cat([fea_3d, geofea_3d], dim=-1) if geofea_3d is not None else fea_3d                    # :269-272
         color, depth = r(obj_cls, fea_cat, T=Ti, K=K_crop, render_image_size=zs, near=self.near, far=self.far,
                          render_tex=True)                                                                            # :135-137
         depth = depth.detach().masked_fill(depth == -1, 0.0)                                                         # :139 (no host sync)
-        c3 = fea_3d.shape[-1]
-        if geofea_3d is not None:
-            syn_img, cfea, geofea1 = torch.split(color, [3, c3, geofea_3d.shape[-1]], dim=1)                         # :277
+        if c3 is None:
+            c3 = color.shape[1] - 3 - cg
+        if cg:
+            syn_img, cfea, geofea1 = torch.split(color, [3, c3, cg], dim=1)                                          # :277
         else:
             syn_img, cfea = torch.split(color, [3, c3], dim=1)
             geofea1 = None
         cfea = (cfea * 0.1).contiguous()                                                                             # :283
-        image_crop = zoom.zoom_crop(image, theta, zs)                                                                # :287
+        # image_index: the objects of one frame crop ONE copy of its image / descriptor map (csrc/zoom_crop.hip, indexed kernel)
+        image_crop = zoom.zoom_crop(image, theta, zs, src_index=image_index)                                         # :287
         geofea2_crop = None
         if geofea1 is not None and geofea_2d is not None:
             geofea1 = geofea1.contiguous()
-            geofea2_crop = zoom.zoom_crop(geofea_2d, theta, zs)                                                      # :291
+            geofea2_crop = zoom.zoom_crop(geofea_2d, theta, zs, src_index=image_index)                               # :291
         syn_depth = depth
         if self.legacy:                                                                                              # :295-304
             syn_depth = r.render_depth(obj_cls, T=Ti, K=K_crop, render_image_size=zs, near=self.near, far=self.far)

@@ -28,6 +28,7 @@ _SCHEMAS = {
     "corr_weight": "(Tensor g1, Tensor g2, Tensor target, Tensor depth, Tensor sigma) -> Tensor",
     "lm_normal_eq": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G) -> (Tensor H, Tensor b)",
     "lm_solve_update": "(Tensor H, Tensor b, Tensor G, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
+    "zoom_crop": "(Tensor x, Tensor theta, int[] crop_size, Tensor? src_index=None) -> Tensor",
     "lm_step": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
 }
 
@@ -80,6 +81,10 @@ def _lm_step(target, weight, depth, K, G, num_iters=1, ep_lambda=100.0, lm_lambd
     return Gn.reshape(G.shape), xi
 
 
+def _zoom_crop(x, theta, crop_size, src_index=None):
+    return ops.zoom_crop(x, theta, crop_size, src_index=src_index)
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
 def _f_corr_pyramid(fmap1, fmap2, levels=4):
     B, _, h, w = fmap1.shape
@@ -119,6 +124,10 @@ def _f_lm_step(target, weight, depth, K, G, num_iters=1, ep_lambda=100.0, lm_lam
     return G.new_empty(G.shape, dtype=torch.float32), G.new_empty((depth.shape[0], 6), dtype=torch.float32)
 
 
+def _f_zoom_crop(x, theta, crop_size, src_index=None):
+    return x.new_empty((theta.shape[0], x.shape[1], int(crop_size[0]), int(crop_size[1])), dtype=torch.float32)
+
+
 def register():
     """Define the `rnnpose` operator library and attach the HIP kernels (CUDA dispatch key) and fake implementations."""
     global _lib
@@ -128,7 +137,8 @@ def register():
     impls = {"corr_pyramid": (_corr_pyramid, _f_corr_pyramid), "corr_lookup": (_corr_lookup, _f_corr_lookup),
              "convex_upsample": (_convex_upsample, _f_convex_upsample), "induced_flow": (_induced_flow, _f_induced_flow),
              "corr_weight": (_corr_weight, _f_corr_weight), "lm_normal_eq": (_lm_normal_eq, _f_lm_normal_eq),
-             "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step)}
+             "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step),
+             "zoom_crop": (_zoom_crop, _f_zoom_crop)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

@@ -22,9 +22,10 @@ def gen_zoom_crop_grids(fg_depth, K, T, output_size, margin_ratio=0.4, want_grid
     return grids, K_crop, theta
 
 
-def zoom_crop(x, theta, crop_size):
-    """F.grid_sample(x, F.affine_grid(theta, ...)) in one kernel (PoseRefiner.py:286-291)."""
-    return ops.zoom_crop(x.float().contiguous(), theta, crop_size)
+def zoom_crop(x, theta, crop_size, src_index=None):
+    """F.grid_sample(x, F.affine_grid(theta, ...)) in one kernel (PoseRefiner.py:286-291).  src_index (ops.SourceIndex or B
+    integers): crop b reads x[src_index[b]] of x (S,C,H,W) -- the objects of one frame share its image; None: crop b reads x[b]."""
+    return ops.zoom_crop(x.float().contiguous(), theta, crop_size, src_index=src_index)
 
 
 def render_pointcloud(verts_per_image, T, K, render_image_size):

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""One camera frame with several different objects, refined two ways on the same items (device events, medians after warm-up):
+
+  (a) one B = 1 `HipEpoch.refine` call per object -- what a one-class-per-batch refiner offers: the 2-D descriptor network, a copy of
+      the image and of its descriptor map, and a PoseRefiner call at B = 1, once per object;
+  (b) one `HipEpoch.refine_frame` call: the descriptor network once, one shared image, one PoseRefiner call at B = objects.
+
+    python tools/scene_bench.py [--objects 8] [--runs 20] [--warmup 3] [--size 480,640] [--out profiles/scene_bench.json]
+
+The two are timed alternately inside every run.  The parts are timed the same way on their own: the descriptor network (per object
+/ once), the two zoom crops of the three outer iterations (B = 1 plain launches per object / one indexed launch per map), and the
+PoseRefiner call with the descriptors given; "refinement" is that call without its crops.  The frame's image and descriptor map
+live on the device throughout (a camera pipeline hands them over there), so no timing contains a host-to-device copy of them.
+Objects: ellipsoids of 2562 vertices / 5120 faces with hash-generated 256 + 32 vertex features, 3 x 4 schedule, random weights."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from rnnpose_amd import eval_epoch as ee, ops  # noqa: E402
+from rnnpose_amd.descriptor2d import SuperPoint2D  # noqa: E402
+from rnnpose_amd.pose_refiner import default_config  # noqa: E402
+
+NAMES = ("ape", "can", "cat", "driller", "duck", "eggbox", "glue", "holepuncher", "benchvise", "camera", "iron", "lamp", "phone")
+
+
+def time_alternately(fns, runs, warmup):
+    """{name: fn} -> {name: dict(median_ms, min_ms, max_ms)}; every run times each fn once, in turn"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(runs):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1))
+    return {k: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for k, v in ts.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--objects", type=int, default=8)
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--size", default="480,640")
+    ap.add_argument("--sub", type=int, default=4, help="icosphere subdivisions of the object meshes (4: 2562 vertices)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("scene_bench measures on the GPU; none is visible")
+    H, W = (int(v) for v in a.size.split(","))
+    n = a.objects
+    torch.manual_seed(0)
+    models = ee.synthetic_models(NAMES[:min(n, len(NAMES))], sub=a.sub)
+    cfg = default_config(RENDER_ITER_COUNT=3, ITER_COUNT=4, OPTIM_ITER_COUNT=1, render_image_size=(H, W), zoom_crop_size=(240, 240))
+    net = SuperPoint2D(dict(input_dim=3, descriptor_dim=32, normalize_output=True, use_instance_norm=True), compute_scores=False).cuda().eval()
+    hip = ee.HipEpoch(models, cfg=cfg, desc2d=net)
+    items = ee.synthetic_scenes(models, 1, n, image_size=(H, W), seed=3, renderer=hip.renderer)
+    image_dev, g2_dev = items[0].image.cuda(), items[0].geofea_2d.cuda()
+    mk = lambda it, g2: ee.EvalItem(it.class_name, image_dev, it.K, it.pose_init, it.pose_gt, g2, frame_id=it.frame_id)
+    given, bare = [mk(it, g2_dev) for it in items], [mk(it, None) for it in items]
+    cover = float((items[0].image.sum(0) > 0).float().mean())
+
+    per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
+    whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
+    refiner = time_alternately({"a_per_object": lambda: per_object(given), "b_frame": lambda: hip.refine_frame(given)}, a.runs, a.warmup)
+
+    image, g2 = image_dev[None].float().contiguous(), g2_dev[None].float().contiguous()
+    desc = time_alternately({"a_per_object": lambda: [net.descriptors(image) for _ in range(n)], "b_frame": lambda: net.descriptors(image)},
+                            a.runs, a.warmup)
+    u = np.random.default_rng(0).uniform(size=(n, 4)).astype(np.float32)
+    theta = torch.zeros(n, 2, 3)
+    theta[:, 0, 0] = theta[:, 1, 1] = torch.from_numpy(0.25 + 0.15 * u[:, 0])
+    theta[:, 0, 2], theta[:, 1, 2] = torch.from_numpy(u[:, 1] - 0.5), torch.from_numpy(u[:, 2] - 0.5)
+    theta = theta.cuda()
+    zs, outer = (240, 240), cfg.RENDER_ITER_COUNT
+    idx = ops.SourceIndex([0] * n, 1, "cuda")
+
+    def crops_a():          # per object: its own copy of both maps is what (a) crops; the copies themselves are part of (a)'s refine
+        for _ in range(outer):
+            for b in range(n):
+                ops.zoom_crop(image, theta[b:b + 1], zs)
+                ops.zoom_crop(g2, theta[b:b + 1], zs)
+
+    def crops_b():
+        for _ in range(outer):
+            ops.zoom_crop(image, theta, zs, src_index=idx)
+            ops.zoom_crop(g2, theta, zs, src_index=idx)
+    crops = time_alternately({"a_per_object": crops_a, "b_frame": crops_b}, a.runs, a.warmup)
+
+    med = lambda r, k: r[k]["median_ms"]
+    parts = {}
+    for k in ("a_per_object", "b_frame"):
+        tot = med(whole, k)
+        parts[k] = dict(total_ms=tot, superpoint2d_ms=med(desc, k), crops_ms=med(crops, k),
+                        refinement_ms=med(refiner, k) - med(crops, k),
+                        superpoint2d_share=med(desc, k) / tot, crops_share=med(crops, k) / tot,
+                        refinement_share=(med(refiner, k) - med(crops, k)) / tot)
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=[H, W], crop=list(zs), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               verts_per_object=int(next(iter(models.values())).verts.shape[0]), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               whole=whole, refiner_call_descriptors_given=refiner, superpoint2d=desc, crops_3_outer_iterations=crops,
+               ratio_a_over_b=med(whole, "a_per_object") / med(whole, "b_frame"), parts=parts,
+               note="refinement = PoseRefiner call with descriptors given minus the crops timed alone; the parts are timed in "
+                    "isolation, so they need not add up to the total exactly")
+    print(f"(a) {n} x B=1 refine : {med(whole, 'a_per_object'):8.2f} ms   (b) one refine_frame : {med(whole, 'b_frame'):8.2f} ms   "
+          f"ratio {res['ratio_a_over_b']:.2f}")
+    for k, p in parts.items():
+        print(f"  {k:13s} SuperPoint2D {p['superpoint2d_ms']:7.2f} ms ({p['superpoint2d_share']:.0%})  crops {p['crops_ms']:6.3f} ms "
+              f"({p['crops_share']:.1%})  refinement {p['refinement_ms']:7.2f} ms ({p['refinement_share']:.0%})")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
