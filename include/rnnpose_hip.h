@@ -593,7 +593,10 @@ int rnnpose_zoom_crop_indexed_f32(const float* in, const int* src_index, const f
  * indices, models back to back; image b uses vertices from vert_off[b], faces [face_off[b], face_off[b] + face_cnt[b])
  * (device int32 arrays of B entries); T (B,4,4) object->camera, K (B,3,3).  A pixel (x, y) samples the ray through
  * (x + pixel_center, y + pixel_center) (PyTorch3D: 0.5); the nearest face by interpolated camera z wins, equal depths go
- * to the lower face index; faces with a vertex at z <= near are dropped.
+ * to the lower face index; faces with a vertex at z <= near are dropped whole (not clipped), and so are faces whose doubled
+ * screen area is <= 1e-8 px^2 or not finite (zero-area faces, a NaN / Inf pose).  Coverage is INCLUSIVE: a pixel centre on an
+ * edge or a vertex belongs to every face that touches it (no holes along shared edges; the nearest / lowest-index one wins).
+ * A face of any screen extent is walked over its bounding box clamped to the image.
  * rnnpose_raster_mesh_f32: pass 1, fills the z-buffer `workspace` (rnnpose_raster_workspace_bytes).
  * rnnpose_raster_resolve_f32: pass 2 from the same workspace and geometry arguments:
  *   out_zbuf   (B,1,H,W)  interpolated depth, `empty_depth` where no face covers the pixel (the reference uses -1);

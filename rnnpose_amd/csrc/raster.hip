@@ -4,7 +4,8 @@
 // perspective-correct barycentrics + interpolate_face_attributes; `render_depth`: nearest-vertex depth).
 // PARITY UNPINNED: PyTorch3D is not in this image and the reference holds no fixture for it; semantics follow PyTorch3D's
 // documented ones (pixel centres at +0.5, nearest face by interpolated camera z, ties -> lower face index) and are checked
-// against oracle/raster_oracle.py and through properties (tests/test_raster.py).
+// against oracle/raster_oracle.py and through properties (tests/test_raster.py), and against an fp64 ray caster and closed-form
+// images at the edge cases (tests/test_gpu_raster_edges.py: inclusive edges, ties, clipping, the near plane, attribute paths).
 //
 // Two passes, no sorting, no per-pixel face lists:
 //   1. raster_faces_kernel: one thread per (image, face).  The face is projected, its screen bounding box walked, and for
@@ -107,8 +108,11 @@ __global__ __launch_bounds__(128) void raster_faces_kernel(const float* __restri
   const float xmin = fminf(fminf(t.x[0], t.x[1]), t.x[2]), xmax = fmaxf(fmaxf(t.x[0], t.x[1]), t.x[2]);
   const float ymin = fminf(fminf(t.y[0], t.y[1]), t.y[2]), ymax = fmaxf(fmaxf(t.y[0], t.y[1]), t.y[2]);
   if (!(xmax >= 0.f && ymax >= 0.f && xmin < static_cast<float>(W) && ymin < static_cast<float>(H))) return;
-  const int x0 = max(0, static_cast<int>(floorf(xmin - pix_center))), x1 = min(W - 1, static_cast<int>(ceilf(xmax - pix_center)));
-  const int y0 = max(0, static_cast<int>(floorf(ymin - pix_center))), y1 = min(H - 1, static_cast<int>(ceilf(ymax - pix_center)));
+  // clamped to the image IN FLOAT: a face just beyond `near` projects past +-2^31 pixels, where float -> int is undefined
+  const int x0 = static_cast<int>(fmaxf(floorf(xmin - pix_center), 0.f));
+  const int x1 = static_cast<int>(fminf(ceilf(xmax - pix_center), static_cast<float>(W - 1)));
+  const int y0 = static_cast<int>(fmaxf(floorf(ymin - pix_center), 0.f));
+  const int y1 = static_cast<int>(fminf(ceilf(ymax - pix_center), static_cast<float>(H - 1)));
   unsigned long long* img = zb + static_cast<long long>(b) * H * W;
   for (int y = y0; y <= y1; ++y)
     for (int x = x0; x <= x1; ++x) {
