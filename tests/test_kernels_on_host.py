@@ -199,7 +199,8 @@ DESELECT = [
     "tests/test_gpu_parity.py::test_update_engine_one_step[False-True-zr=3,zr2=3,heads=3,q=1,conv=2]",
 ]
 FILES = ["tests/test_gpu_parity.py", "tests/test_gpu_conv.py", "tests/test_gpu_eval.py", "tests/test_zoom.py", "tests/test_raster.py",
-         "tests/test_gpu_lm_geometry.py", "tests/test_gpu_raster_edges.py"]      # (their large shapes carry `full_size` in their names: PARITY_K leaves them out)
+         "tests/test_gpu_lm_geometry.py", "tests/test_gpu_raster_edges.py",      # (their large shapes carry `full_size` in their names: PARITY_K leaves them out)
+         "tests/test_gpu_zoom_edges.py"]                                         # (no large shapes: the whole module runs here)
 
 # The strip convolution kernels (LDS-DMA by inline assembly on the GPU; tests/host_exec/build_host.py gives their scratch copy host
 # versions of the request / wait helpers): both strip heights, split-tensor (DMA) and fp32 (register-path) sources, 3x3 / 1x5 / 5x1,
@@ -259,7 +260,7 @@ def test_gpu_parity_tests_pass_on_the_host_executed_kernels(host_lib):
     a = _subset(host_lib, ["-k", PARITY_K] + [x for d in DESELECT for x in ("--deselect", d)] + FILES)
     b = _subset(host_lib, STRIP_IDS)
     _passed(b, len(STRIP_IDS))
-    _passed(a, 95 + 88 + 70)          # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py
+    _passed(a, 95 + 88 + 70 + 94)     # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py, 94: all of tests/test_gpu_zoom_edges.py
 
 
 def test_harness_model(tmp_path):
