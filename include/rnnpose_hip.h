@@ -635,6 +635,27 @@ int rnnpose_raster_resolve_tex_f32(const float* verts, const int* faces, const i
                                    const long long* tex_off, const int* tex_hw, const float* vnormals, int shade,
                                    float empty_depth, float* out_attr, float* out_zbuf, float* out_vdepth,
                                    rnnpose_stream_t stream);
+/* rnnpose_raster_occlusion_f32: which pixels of every object's own view are hidden by ANOTHER object of the same batch.
+ *   Geometry, T, K, near, pixel_center as rnnpose_raster_mesh_f32; K[b] is the (crop) window of object b's view.
+ *   pair_target / pair_occluder (P) device int32, P <= 65535: pair (b, j) rasterises object j under ITS pose T[j] into the
+ *     window K[b] of object b, with the coverage and depth arithmetic of rnnpose_raster_mesh_f32 at perspective_correct = 1
+ *     (inclusive edges, faces reaching behind `near` and degenerate faces dropped whole).  A pair with an index outside [0,B) or
+ *     with b == j writes nothing.  P = 0 is valid: nothing is hidden.
+ *   own_keys: the workspace rnnpose_raster_mesh_f32 filled for the same B, H, W, T, K with perspective_correct = 1 (read only);
+ *   workspace: a second buffer of rnnpose_raster_workspace_bytes(B, H, W) bytes, distinct from own_keys (overwritten).
+ *   With z_own the depth of object b's own nearest face at a pixel and D the smallest depth any of its occluders reaches there,
+ *   the pixel is OCCLUDED iff both exist and D + margin < z_own (fp32, one addition, strict): margin is in the meshes' length
+ *   unit; an occluder at exactly the own depth hides nothing at margin 0.
+ *   visible    (B,1,H,W) fp32   1 where the object covers the pixel and is not occluded there, else 0 (every pixel written);
+ *   occluder   (B,1,H,W) int32  batch index of the nearest occluder where occluded (the lower index on equal depths), else -1
+ *                               (every pixel written); may be NULL;
+ *   depth_inout (B,1,H,W) fp32  occluded pixels are set to 0, every other pixel is left as it is; may be NULL.
+ *   Three launches on `stream` (clear, occluder pass [P > 0], apply); no allocation, no synchronisation. */
+int rnnpose_raster_occlusion_f32(const float* verts, const int* faces, const int* vert_off, const int* face_off,
+                                 const int* face_cnt, int max_faces, const float* T, const float* K, int B, int H, int W,
+                                 float near, float pixel_center, const int* pair_target, const int* pair_occluder, int P,
+                                 float margin, const void* own_keys, void* workspace, size_t workspace_bytes, float* visible,
+                                 int* occluder, float* depth_inout, rnnpose_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,9 @@
 //   2'. raster_resolve_tex_kernel (render_tex with a UV texture or Phong shading): the same pass, with the colour taken from
 //      the mesh's texture map at the interpolated UV (one bilinear grid_sample, four 16-byte RGBA taps) and shaded per pixel
 //      with interpolated vertex normals (PyTorch3D's SoftPhongShader with faces_per_pixel = 1).
+// Occlusion between the objects of one frame (rnnpose_raster_occlusion_f32; no counterpart in the reference, which refines one class
+// per batch): raster_occluder_kernel z-buffers, for every (target, occluder) pair, the occluder's faces into the target's window with
+// the arithmetic of pass 1, and raster_occlusion_apply_kernel compares that buffer with the target's own keys per pixel.
 #include "common.hpp"
 
 namespace {
@@ -357,6 +360,70 @@ __global__ __launch_bounds__(256) void raster_resolve_tex_kernel(
   for (; c < C; ++c) o[c * P] = hit ? w0 * a0[c] + w1 * a1[c] + w2 * a2[c] : 0.f;
 }
 
+// ---- occlusion between the objects of one frame (rnnpose_raster_occlusion_f32) ------------------------------------------------
+// Occluder pass: one thread per (pair, face of the occluder).  For pair (b, j) the faces of object j are projected with ITS pose
+// T[j] into the crop window of the target, K[b], and z-buffered into image b of a second key buffer with the arithmetic of
+// raster_faces_kernel (project_face / bary_at, perspective-correct, inclusive edges, float-clamped boxes); the low half of the key
+// is j instead of the face index, so the nearest occluder wins and equal depths go to the lower batch index.
+__global__ __launch_bounds__(128) void raster_occluder_kernel(const float* __restrict__ verts, const int* __restrict__ faces,
+                                                              const int* __restrict__ vert_off, const int* __restrict__ face_off,
+                                                              const int* __restrict__ face_cnt, const float* __restrict__ T,
+                                                              const float* __restrict__ K, const int* __restrict__ pair_target,
+                                                              const int* __restrict__ pair_occluder, int B, int H, int W, float near,
+                                                              float pix_center, unsigned long long* __restrict__ zb) {
+  const int p = blockIdx.y;
+  const int b = pair_target[p], j = pair_occluder[p];
+  if (b < 0 || b >= B || j < 0 || j >= B || b == j) return;      // the second fence (the host refuses such pairs first)
+  const int fl = blockIdx.x * 128 + threadIdx.x;
+  if (fl >= face_cnt[j]) return;
+  Cam c = load_cam(T, K, j);                                     // the occluder's pose ...
+  const float* k = K + 9 * b;                                    // ... seen through the target's crop window
+  c.fx = k[0]; c.fy = k[4]; c.cx = k[2]; c.cy = k[5];
+  const long long f = static_cast<long long>(face_off[j]) + fl;
+  const Tri t = project_face(verts, faces, f, vert_off[j], c, near);
+  if (!t.ok) return;
+  const float xmin = fminf(fminf(t.x[0], t.x[1]), t.x[2]), xmax = fmaxf(fmaxf(t.x[0], t.x[1]), t.x[2]);
+  const float ymin = fminf(fminf(t.y[0], t.y[1]), t.y[2]), ymax = fmaxf(fmaxf(t.y[0], t.y[1]), t.y[2]);
+  if (!(xmax >= 0.f && ymax >= 0.f && xmin < static_cast<float>(W) && ymin < static_cast<float>(H))) return;
+  const int x0 = static_cast<int>(fmaxf(floorf(xmin - pix_center), 0.f));
+  const int x1 = static_cast<int>(fminf(ceilf(xmax - pix_center), static_cast<float>(W - 1)));
+  const int y0 = static_cast<int>(fmaxf(floorf(ymin - pix_center), 0.f));
+  const int y1 = static_cast<int>(fminf(ceilf(ymax - pix_center), static_cast<float>(H - 1)));
+  unsigned long long* img = zb + static_cast<long long>(b) * H * W;
+  for (int y = y0; y <= y1; ++y)
+    for (int x = x0; x <= x1; ++x) {
+      float w0, w1, w2, z;
+      if (bary_at(t, static_cast<float>(x) + pix_center, static_cast<float>(y) + pix_center, 1, w0, w1, w2, z)) {
+        const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(z)) << 32) | static_cast<unsigned>(j);
+        atomicMin(img + static_cast<long long>(y) * W + x, key);
+      }
+    }
+}
+
+// the depth test, op by op in fp32: an occluder at exactly the own depth (margin 0) hides nothing
+__device__ __forceinline__ bool occluder_in_front(float D, float margin, float z_own) {
+#pragma clang fp contract(off)
+  const float d = D + margin;
+  return d < z_own;
+}
+
+// Apply pass: one thread per pixel of every image reads the own key and the occluder key and writes all of visible / occluder.
+__global__ __launch_bounds__(256) void raster_occlusion_apply_kernel(const unsigned long long* __restrict__ own,
+                                                                     const unsigned long long* __restrict__ occ, long long n,
+                                                                     float margin, float* __restrict__ visible,
+                                                                     int* __restrict__ occluder, float* __restrict__ depth_inout) {
+  const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long ko = own[i], kj = occ[i];
+  const bool hit = ko != kEmpty;
+  bool hidden = false;
+  if (hit && kj != kEmpty)
+    hidden = occluder_in_front(__uint_as_float(static_cast<unsigned>(kj >> 32)), margin, __uint_as_float(static_cast<unsigned>(ko >> 32)));
+  visible[i] = (hit && !hidden) ? 1.0f : 0.0f;
+  if (occluder) occluder[i] = hidden ? static_cast<int>(static_cast<unsigned>(kj & 0xffffffffull)) : -1;
+  if (depth_inout && hidden) depth_inout[i] = 0.0f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -423,6 +490,31 @@ int rnnpose_raster_resolve_tex_f32(const float* verts, const int* faces, const i
                      static_cast<const unsigned long long*>(workspace), attr, attr_off, C, colors, uvs, face_uvs, uv_off,
                      reinterpret_cast<const float4*>(tex), tex_off, tex_hw, vnormals, shade, empty_depth, out_attr, out_zbuf,
                      out_vdepth);
+  return rp::check_launch(fn);
+}
+
+int rnnpose_raster_occlusion_f32(const float* verts, const int* faces, const int* vert_off, const int* face_off,
+                                 const int* face_cnt, int max_faces, const float* T, const float* K, int B, int H, int W,
+                                 float near, float pixel_center, const int* pair_target, const int* pair_occluder, int P,
+                                 float margin, const void* own_keys, void* workspace, size_t workspace_bytes, float* visible,
+                                 int* occluder, float* depth_inout, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_raster_occlusion_f32";
+  RP_REQUIRE(verts && faces && vert_off && face_off && face_cnt && T && K && own_keys && workspace && visible, fn, "null pointer");
+  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && max_faces > 0 && near > 0.f, fn, "bad size");
+  RP_REQUIRE(P >= 0 && P <= 65535, fn, "pair count must lie in [0, 65535]");
+  RP_REQUIRE(P == 0 || (pair_target && pair_occluder), fn, "pairs need pair_target and pair_occluder");
+  RP_REQUIRE(margin == margin, fn, "margin is NaN");
+  RP_REQUIRE(own_keys != workspace, fn, "the occluder workspace must not be the own key buffer");
+  RP_REQUIRE(workspace_bytes >= rnnpose_raster_workspace_bytes(B, H, W), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  unsigned long long* zb = static_cast<unsigned long long*>(workspace);
+  const long long n = static_cast<long long>(B) * H * W;
+  hipLaunchKernelGGL(raster_clear_kernel, dim3(rp::cdiv(n, 256)), dim3(256), 0, st, zb, n);
+  if (P > 0)
+    hipLaunchKernelGGL(raster_occluder_kernel, dim3(rp::cdiv(max_faces, 128), P), dim3(128), 0, st, verts, faces, vert_off, face_off,
+                       face_cnt, T, K, pair_target, pair_occluder, B, H, W, near, pixel_center, zb);
+  hipLaunchKernelGGL(raster_occlusion_apply_kernel, dim3(rp::cdiv(n, 256)), dim3(256), 0, st,
+                     static_cast<const unsigned long long*>(own_keys), zb, n, margin, visible, occluder, depth_inout);
   return rp::check_launch(fn);
 }
 

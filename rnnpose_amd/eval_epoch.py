@@ -149,7 +149,11 @@ def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8
 class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
-    def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None):
+    def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None, occlusion=None,
+                 occlusion_margin=0.0):
+        """occlusion="frame" (PoseRefiner's argument; occlusion_margin in the models' length unit): refine_frame masks the pixels of
+        every object that another object of the same frame hides under the current pose estimates.  `refine` -- one class per
+        batch, one image per object -- has no pairs and is unaffected.  With a ready-made `refiner`, set it there."""
         from .evaluator import LineMODEvaluator
         from .pose_refiner import PoseRefiner, default_config
         from .rasterizer import MeshRenderer
@@ -161,7 +165,10 @@ class HipEpoch:
                                               faces_uvs=m.faces_uvs, texture=m.texture) for n, m in models.items()},
                                      device=device, shading=shading)
         self.cfg = cfg if cfg is not None else default_config()
-        self.refiner = refiner if refiner is not None else PoseRefiner(self.cfg, renderer=self.renderer).to(self.device).eval()
+        if refiner is not None and occlusion is not None:
+            raise ValueError("HipEpoch(refiner=..., occlusion=...): construct the refiner with occlusion= instead")
+        self.refiner = refiner if refiner is not None else \
+            PoseRefiner(self.cfg, renderer=self.renderer, occlusion=occlusion, occlusion_margin=occlusion_margin).to(self.device).eval()
         self.symmetric = tuple(symmetric)
         # desc2d: a descriptor2d.SuperPoint2D -- items without geofea_2d get theirs from the batch image on the device, as
         # model/RNNPose.py:162 computes them (HybridNet.py:97 keeps the descriptors only)

@@ -1593,3 +1593,107 @@ def zoom_crop(x, theta, crop_size, want_grid=False, src_index=None):
     grid = torch.empty(B, hc, wc, 2, device=theta.device, dtype=F32) if want_grid else None
     _launch("rnnpose_zoom_crop_f32", _ptr(x), _ptr(theta), B, C_, H, W, hc, wc, _ptr(out), _ptr(grid), _stream())
     return (out, grid) if want_grid else out
+
+
+# ---- occlusion between the objects of one frame ------------------------------------------------------------------------
+class OcclusionPairs:
+    """Which objects of a batch may hide which (`raster_occlusion`, `MeshRenderer.occlusion`): all ORDERED pairs (b, j), b != j, of
+    objects that crop the same source image -- target b, occluder j.  Objects are paired by batch index, not by class: two instances
+    of one class occlude each other.  image_index: an ops.SourceIndex, B integers, or None = every object has its own image = no
+    pairs.  Checked ON THE HOST once (ValueError); holds the device copies the kernel reads.  Build it once per batch."""
+
+    MAX_PAIRS = 65535
+
+    def __init__(self, image_index, B, device):
+        B = int(B)
+        if image_index is None:
+            pairs = []
+        else:
+            host = image_index.host if isinstance(image_index, SourceIndex) else tuple(int(v) for v in (
+                image_index.detach().cpu().tolist() if isinstance(image_index, torch.Tensor) else image_index))
+            if len(host) != B:
+                raise ValueError(f"image_index names {len(host)} objects, the batch holds {B}")
+            pairs = [(b, j) for b in range(B) for j in range(B) if b != j and host[b] == host[j]]
+        self._set(pairs, B, device)
+
+    @classmethod
+    def from_pairs(cls, pairs, B, device):
+        """An explicit list of (target, occluder) batch indices; every index in [0, B) and target != occluder, else ValueError."""
+        self = cls.__new__(cls)
+        self._set([(int(b), int(j)) for b, j in pairs], int(B), device)
+        return self
+
+    def _set(self, pairs, B, device):
+        if B < 1:
+            raise ValueError(f"OcclusionPairs: B must be positive, got {B}")
+        bad = [(b, j) for b, j in pairs if not (0 <= b < B and 0 <= j < B) or b == j]
+        if bad:
+            raise ValueError(f"occlusion pairs must name two different objects in [0, {B}): got {bad[:4]}")
+        if len(pairs) > self.MAX_PAIRS:
+            raise ValueError(f"{len(pairs)} occlusion pairs: one call takes at most {self.MAX_PAIRS}")
+        self.B = B
+        self.host = tuple(pairs)
+        self.target = torch.tensor([p[0] for p in pairs], dtype=torch.int32, device=device)
+        self.occluder = torch.tensor([p[1] for p in pairs], dtype=torch.int32, device=device)
+
+    def __len__(self):
+        return len(self.host)
+
+
+def _i32_dev(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+        raise RuntimeError(f"{name} must be a contiguous int32 GPU tensor")
+    return t
+
+
+def raster_keys(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, size, near=0.1, pixel_center=0.5, perspective=True):
+    """Pass 1 of the mesh rasteriser (rnnpose_raster_mesh_f32) -> the (B*H*W,) int64 key buffer the resolve passes and
+    `raster_occlusion` read.  Geometry as in include/rnnpose_hip.h: all meshes back to back, per-image offsets."""
+    B, H, W = int(T.shape[0]), int(size[0]), int(size[1])
+    n = int(_lib.load().rnnpose_raster_workspace_bytes(B, H, W))
+    ws = torch.empty(n // 8, dtype=torch.int64, device=T.device)
+    _launch("rnnpose_raster_mesh_f32", _ptr(verts), _ptr(faces), _ptr(vert_off), _ptr(face_off), _ptr(face_cnt), int(max_faces),
+            _ptr(T), _ptr(K), B, H, W, float(near), float(pixel_center), int(perspective), _ptr(ws), n, _stream())
+    return ws
+
+
+def raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, size, pairs: OcclusionPairs, margin: float = 0.0,
+                     near: float = 0.1, pixel_center: float = 0.5, own_keys=None, depth=None, want_occluder: bool = True):
+    """Which pixels of every object's own view another object of the batch hides (rnnpose_raster_occlusion_f32).
+    verts (V,3) fp32, faces (F,3) int32, vert_off / face_off / face_cnt (B,) int32: the rasteriser's geometry; T (B,4,4), K (B,3,3)
+    the poses and (crop) intrinsics of the own views; size (H, W); pairs: an OcclusionPairs built for this batch.
+    Pixel of object b is occluded iff an occluder j of b reaches depth D there with D + margin < z_own (strict, fp32); margin is in
+    the meshes' length unit, 0 = the pure depth test.
+    own_keys: the key buffer of `raster_keys` for the same T, K, size with perspective=True (None: rasterised here).
+    depth (B,1,H,W) fp32 contiguous: occluded pixels are set to 0 IN PLACE, the others are not touched.
+    -> visible (B,1,H,W) fp32 in {0, 1} (own coverage and not occluded), occluder (B,1,H,W) int32 (-1 = not occluded) or None."""
+    if not isinstance(pairs, OcclusionPairs):
+        raise TypeError("pairs must be an ops.OcclusionPairs")
+    verts, T, K = _chk(verts, "verts"), _chk(T, "T"), _chk(K, "K")
+    faces = _i32_dev(faces, "faces")
+    vert_off, face_off, face_cnt = _i32_dev(vert_off, "vert_off"), _i32_dev(face_off, "face_off"), _i32_dev(face_cnt, "face_cnt")
+    B, H, W = int(T.shape[0]), int(size[0]), int(size[1])
+    if pairs.B != B:
+        raise ValueError(f"the occlusion pairs were built for {pairs.B} objects, the poses hold {B}")
+    if T.shape[1:] != (4, 4) or K.shape != (B, 3, 3) or min(vert_off.numel(), face_off.numel(), face_cnt.numel()) < B:
+        raise ValueError("raster_occlusion: T (B,4,4), K (B,3,3) and B entries of vert_off / face_off / face_cnt")
+    margin = float(margin)
+    if margin != margin:
+        raise ValueError("raster_occlusion: margin is NaN")
+    if depth is not None:
+        if not (depth.is_cuda and depth.dtype == F32 and depth.is_contiguous() and depth.numel() == B * H * W):
+            raise ValueError(f"depth must be a contiguous fp32 GPU tensor of {B} x {H} x {W} pixels")
+    n = int(_lib.load().rnnpose_raster_workspace_bytes(B, H, W))
+    if own_keys is None:
+        own_keys = raster_keys(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, (H, W), near, pixel_center, True)
+    elif not (own_keys.is_cuda and own_keys.is_contiguous() and own_keys.numel() * own_keys.element_size() >= n):
+        raise ValueError("own_keys must be the key buffer of raster_keys for this batch and size")
+    ws = torch.empty(n // 8, dtype=torch.int64, device=T.device)
+    visible = torch.empty(B, 1, H, W, device=T.device, dtype=F32)
+    occluder = torch.empty(B, 1, H, W, device=T.device, dtype=torch.int32) if want_occluder else None
+    P = len(pairs)
+    _launch("rnnpose_raster_occlusion_f32", _ptr(verts), _ptr(faces), _ptr(vert_off), _ptr(face_off), _ptr(face_cnt), int(max_faces),
+            _ptr(T), _ptr(K), B, H, W, float(near), float(pixel_center), _ptr(pairs.target if P else None),
+            _ptr(pairs.occluder if P else None), P, margin, _ptr(own_keys), _ptr(ws), n, _ptr(visible), _ptr(occluder), _ptr(depth),
+            _stream())
+    return visible, occluder

@@ -79,8 +79,13 @@ class SynImgTail:
 class PoseRefiner(nn.Module):
     def __init__(self, cfg=None, reuse=False, schedule=None, use_regressor=True, is_calibrated=True,
                  bn_is_training=False, is_training=True, renderer=None, fused=True,
-                 img_fea_enc_weights=None, use_graph=True, literal_legacy_pose=None):
-        """literal_legacy_pose (or cfg["literal_legacy_pose"]; default True since r06): start every outer iteration from the reference's
+                 img_fea_enc_weights=None, use_graph=True, literal_legacy_pose=None, occlusion=None, occlusion_margin=None):
+        """occlusion (or cfg["occlusion"]; default None) / occlusion_margin (or cfg["occlusion_margin"]; default 0): "frame" masks, in
+        every outer iteration, the pixels of each object's synthetic depth that another object of the same frame (same image_index
+        entry) hides under the CURRENT pose estimates of the whole batch (render_adapter.RendererAdapter); the returned dict then
+        carries `occlusion_visible`, the last outer iteration's map.  The pass runs in the eager render hand-off: the loop kernels,
+        the captured graphs and their cache keys are the same with it on or off.
+        literal_legacy_pose (or cfg["literal_legacy_pose"]; default True since r06): start every outer iteration from the reference's
         legacy product Tij = Ti * Ti.inv() (model/PoseRefiner.py:243-244) -- what the reference computes.  False: the exact identity
         that product stands for (the r03-r05 default; on the reference-generated fixtures it is FURTHER from the reference on three of
         four, and crosses 1e-4 px at 960 x 1280: profiles/r05_fixture_distances.txt)."""
@@ -88,6 +93,10 @@ class PoseRefiner(nn.Module):
         self.legacy = True
         self.cfg = cfg = cfg if cfg is not None else default_config()
         self.literal_legacy_pose = bool(cfg.get("literal_legacy_pose", True) if literal_legacy_pose is None else literal_legacy_pose)
+        self.occlusion = cfg.get("occlusion", None) if occlusion is None else occlusion
+        self.occlusion_margin = float(cfg.get("occlusion_margin", 0.0) if occlusion_margin is None else occlusion_margin)
+        if self.occlusion not in (None, "frame"):
+            raise ValueError(f'occlusion must be None or "frame", got {self.occlusion!r}')
         self.reuse = reuse
         self.sigma = nn.ParameterList([nn.Parameter(torch.ones(1) * 1)])
         self.with_corr_weight = cfg.get("with_corr_weight", True)
@@ -103,7 +112,11 @@ class PoseRefiner(nn.Module):
             # constructed as PoseRefiner(opt.motion_net, ..., renderer=diff_renderer) at model/RNNPose.py:76-79)
             from .render_adapter import RendererAdapter
             renderer = RendererAdapter(renderer, render_image_size=cfg.get("render_image_size", (480, 640)),
-                                       zoom_crop_size=cfg.get("zoom_crop_size", (240, 240)), legacy=True)
+                                       zoom_crop_size=cfg.get("zoom_crop_size", (240, 240)), legacy=True,
+                                       occlusion=self.occlusion, occlusion_margin=self.occlusion_margin)
+        elif self.occlusion is not None and getattr(renderer, "occlusion", None) != self.occlusion:
+            raise ValueError('occlusion="frame" is served by RendererAdapter: pass a renderer with the reference call shape, or an '
+                             "adapter constructed with the same occlusion setting")
         self.renderer = renderer
         self.fused = fused
         # hipGraph replay of the inner-iteration body (~25 launches): at the reference's own working size (B=1,
@@ -433,6 +446,8 @@ class PoseRefiner(nn.Module):
                                geofea_2d=geofea_2d, image_index=image_index)
         if image_index is not None:
             views_kw["image_index"] = image_index
+        if getattr(self.renderer, "occlusion", None) == "frame":     # the pairs of the batch, checked and uploaded once per forward
+            views_kw["occlusion_pairs"] = ops.OcclusionPairs(image_index, Ts.G.shape[0], intrinsics.device)
         if image is not None and image.is_cuda or intrinsics.is_cuda:
             from .streams import reserve
             reserve(intrinsics.device)        # bind the concurrent streams to distinct hardware queues before anything else
@@ -527,7 +542,9 @@ class PoseRefiner(nn.Module):
                     Tij_gt.append((Tj_gt * Ti.inv()).copy(stop_gradients=True))
 
         Ti = Tij * Ti                                                   # final update (:365)
+        extra = {"occlusion_visible": views["occlusion_visible"]} if "occlusion_visible" in views else {}
         return {
+            **extra,
             "Tij": Tij,
             "Ti_pred": Ti,
             "intrinsics": intrinsics,

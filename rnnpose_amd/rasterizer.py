@@ -329,3 +329,29 @@ class MeshRenderer:
         out, zb, _ = self._resolve(bt, T, K, render_image_size, near, True, ws, attr=attr, attr_off=attr_off, Cc=Cc,
                                    with_color=bool(render_tex), want_zbuf=True, empty_depth=-1.0)
         return out, zb
+
+    # ---- occlusion between the objects of one frame ------------------------------------------------------------------
+    def occlusion(self, model_names, T, K, render_image_size, pairs, margin=0.0, near=0.1, depth=None, want_occluder=False):
+        """Which pixels of every object's own view are hidden by another object of the same frame (csrc/raster.hip,
+        rnnpose_raster_occlusion_f32).  T (B,4,4) the poses of ALL objects, K (B,3,3) the (crop) intrinsics of every object's own
+        view, pairs an ops.OcclusionPairs of this batch: for pair (b, j) object j is rasterised under T[j] into the window K[b].
+        A pixel of b is occluded iff an occluder's depth D there satisfies D + margin < z_own, both from the z-buffer arithmetic of
+        __call__ (strict: a coincident surface hides nothing at margin 0).  margin is in the meshes' length unit; 0 is the pure depth
+        test, a positive value keeps pixels whose occluder is less than that far in front.
+        depth (B,1,h,w) fp32: occluded pixels are zeroed in place, all others stay bit for bit.
+        -> visible (B,1,h,w) bool (covered by the object and not occluded) [, occluder (B,1,h,w) int32 batch index, -1 elsewhere].
+        Stateless: the own z-buffer is rasterised here (the same launch as __call__'s first pass)."""
+        if not isinstance(pairs, ops.OcclusionPairs):
+            raise TypeError("pairs must be an ops.OcclusionPairs")
+        bt = self._batch(model_names)
+        T, K = self._tk(T, K)
+        if pairs.B != T.shape[0] or len(model_names) != T.shape[0]:
+            raise ValueError(f"{len(model_names)} models, {T.shape[0]} poses, occlusion pairs of {pairs.B} objects")
+        if float(margin) != float(margin):
+            raise ValueError("occlusion: margin is NaN")
+        keys = self._raster(bt, T, K, render_image_size, near, perspective=True)
+        vis, occ = ops.raster_occlusion(self.verts, self.faces, bt["vert_off"], bt["face_off"], bt["face_cnt"], bt["max_faces"], T, K,
+                                        render_image_size, pairs, margin=margin, near=near, pixel_center=self.pixel_center,
+                                        own_keys=keys, depth=depth, want_occluder=want_occluder)
+        vis = vis > 0
+        return (vis, occ) if want_occluder else vis

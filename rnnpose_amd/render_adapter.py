@@ -27,9 +27,18 @@ from . import zoom
 
 class RendererAdapter:
     def __init__(self, renderer, render_image_size=(480, 640), zoom_crop_size=(240, 240), legacy=True, margin_ratio=0.4,
-                 near=0.1, far=6):
+                 near=0.1, far=6, occlusion=None, occlusion_margin=0.0):
         """render_image_size / zoom_crop_size: `BASIC.render_image_size` / `BASIC.zoom_crop_size` of the reference config
-        (config/default.py:48-49, config/linemod/template_fw0.5.yml:14-15)."""
+        (config/default.py:48-49, config/linemod/template_fw0.5.yml:14-15).
+        occlusion: None (default: every object is refined against its own render alone) or "frame": after the render of every outer
+        iteration, `renderer.occlusion` finds the pixels of each object's synthetic view that ANOTHER object of the same frame (same
+        image_index entry), under its current pose estimate, is in front of, and `syn_depth` is zeroed there -- on the legacy
+        nearest-vertex path and on the z-buffer path alike.  Validity in the refinement loop is `syn_depth > 0`, so those pixels drop
+        out of the descriptor weight, the induced flow and the LM normal equations.  The rendered maps (syn_img, cfea, geofea1) are
+        NOT touched: the encoder still sees the whole object; only validity changes.  The views gain `occlusion_visible`
+        (B,1,h,w) bool and `occluder` (B,1,h,w) int32 (batch index of the nearest occluder, -1 elsewhere).
+        occlusion_margin: in the meshes' length unit; a pixel is hidden iff an occluder's depth D there has D + margin < own depth.
+        0 (default) is the pure depth test; no value has been tuned against a dataset."""
         for name in ("render_pointcloud", "render_depth"):
             if not callable(getattr(renderer, name, None)):
                 raise TypeError(f"renderer must provide {name}() (geometry/diff_render_optim.py:404-494)")
@@ -41,6 +50,10 @@ class RendererAdapter:
         self.legacy = legacy
         self.margin_ratio = float(margin_ratio)
         self.near, self.far = near, far
+        if occlusion not in (None, "frame"):
+            raise ValueError(f'occlusion must be None or "frame", got {occlusion!r}')
+        self.occlusion = occlusion
+        self.occlusion_margin = float(occlusion_margin)
 
     def prepare_inputs(self, B, obj_cls=None, image=None, fea_3d=None, geofea_3d=None, geofea_2d=None, image_index=None):
         """Host-side checks of one PoseRefiner.forward() call, before anything is launched (ValueError on a batch the
@@ -50,6 +63,8 @@ class RendererAdapter:
         list of B per-image (P_b, C) tables, or None when the renderer holds a resident table for every class of obj_cls."""
         from . import ops
         r = self.renderer
+        if self.occlusion is not None and not callable(getattr(r, "occlusion", None)):
+            raise ValueError('occlusion="frame" needs a renderer with an occlusion() method (rnnpose_amd.rasterizer.MeshRenderer)')
         names = getattr(r, "names", None)
         if names is not None and obj_cls is not None:
             unknown = sorted({str(n) for n in obj_cls if n not in names})
@@ -102,9 +117,11 @@ class RendererAdapter:
 
     @torch.no_grad()
     def render_views(self, Ti, intrinsics, obj_cls=None, image=None, fea_3d=None, geofea_3d=None, geofea_2d=None,
-                     image_index=None):
+                     image_index=None, occlusion_pairs=None):
         """Ti (B,4,4) current absolute pose, intrinsics (B,3,3) of the full image -> views dict of one outer iteration.
-        image_index (ops.SourceIndex or B integers; see prepare_inputs): object b crops image / geofea_2d [image_index[b]]."""
+        image_index (ops.SourceIndex or B integers; see prepare_inputs): object b crops image / geofea_2d [image_index[b]].
+        occlusion_pairs (occlusion="frame"): the ops.OcclusionPairs of this batch (PoseRefiner builds them once per forward); None:
+        built here from image_index.  The occluders' poses are the rows of Ti, the current estimates of the whole batch."""
         r, zs = self.renderer, self.zoom_crop_size
         pc_depth = r.render_pointcloud(obj_cls, T=Ti, K=intrinsics, render_image_size=self.render_image_size)       # :253-254
         B = pc_depth.shape[0]
@@ -142,9 +159,28 @@ class RendererAdapter:
         syn_depth = depth
         if self.legacy:                                                                                              # :295-304
             syn_depth = r.render_depth(obj_cls, T=Ti, K=K_crop, render_image_size=zs, near=self.near, far=self.far)
+        extra = {}
+        if self.occlusion == "frame":
+            extra = self._occlude(Ti, K_crop, obj_cls, image_index, occlusion_pairs, syn_depth)
+            syn_depth = extra.pop("syn_depth")
         return dict(syn_img=syn_img.contiguous(), image_crop=image_crop, cfea=cfea, geofea1=geofea1,
                     geofea2_crop=geofea2_crop, syn_depth=syn_depth.contiguous(), intrinsics_crop=K_crop,
-                    fmap1=None, fmap2=None, theta=theta, pc_depth=pc_depth)
+                    fmap1=None, fmap2=None, theta=theta, pc_depth=pc_depth, **extra)
+
+    def _occlude(self, Ti, K_crop, obj_cls, image_index, pairs, syn_depth):
+        """occlusion="frame": zero the pixels of syn_depth another object of the frame hides -> syn_depth, occlusion_visible, occluder.
+        A batch without pairs (no image_index: one image per object) launches nothing: every covered pixel is visible."""
+        from . import ops
+        B = Ti.shape[0]
+        if pairs is None:
+            pairs = ops.OcclusionPairs(image_index, B, Ti.device)
+        if len(pairs) == 0:
+            return dict(syn_depth=syn_depth, occlusion_visible=syn_depth > 0,
+                        occluder=torch.full(syn_depth.shape, -1, dtype=torch.int32, device=syn_depth.device))
+        syn_depth = syn_depth.float().contiguous()
+        vis, occ = self.renderer.occlusion(obj_cls, T=Ti, K=K_crop, render_image_size=self.zoom_crop_size, pairs=pairs,
+                                           margin=self.occlusion_margin, near=self.near, depth=syn_depth, want_occluder=True)
+        return dict(syn_depth=syn_depth, occlusion_visible=vis, occluder=occ)
 
 
 def filter_param_dict(state_dict, include=None, exclude=None):

@@ -29,6 +29,7 @@ _SCHEMAS = {
     "lm_normal_eq": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G) -> (Tensor H, Tensor b)",
     "lm_solve_update": "(Tensor H, Tensor b, Tensor G, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
     "zoom_crop": "(Tensor x, Tensor theta, int[] crop_size, Tensor? src_index=None) -> Tensor",
+    "raster_occlusion": "(Tensor verts, Tensor faces, Tensor vert_off, Tensor face_off, Tensor face_cnt, int max_faces, Tensor T, Tensor K, int[] size, Tensor pair_target, Tensor pair_occluder, float margin=0.0, float near=0.1, float pixel_center=0.5) -> (Tensor visible, Tensor occluder)",
     "lm_step": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
 }
 
@@ -85,6 +86,15 @@ def _zoom_crop(x, theta, crop_size, src_index=None):
     return ops.zoom_crop(x, theta, crop_size, src_index=src_index)
 
 
+def _raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, size, pair_target, pair_occluder, margin=0.0, near=0.1,
+                      pixel_center=0.5):
+    """pair_target / pair_occluder: (P,) integer tensors, checked on the host (ValueError) before anything is launched."""
+    pairs = ops.OcclusionPairs.from_pairs(zip(pair_target.detach().cpu().tolist(), pair_occluder.detach().cpu().tolist()), T.shape[0],
+                                          T.device)
+    return ops.raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, size, pairs, margin=margin, near=near,
+                                pixel_center=pixel_center, want_occluder=True)
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
 def _f_corr_pyramid(fmap1, fmap2, levels=4):
     B, _, h, w = fmap1.shape
@@ -128,6 +138,12 @@ def _f_zoom_crop(x, theta, crop_size, src_index=None):
     return x.new_empty((theta.shape[0], x.shape[1], int(crop_size[0]), int(crop_size[1])), dtype=torch.float32)
 
 
+def _f_raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K, size, pair_target, pair_occluder, margin=0.0, near=0.1,
+                        pixel_center=0.5):
+    shape = (T.shape[0], 1, int(size[0]), int(size[1]))
+    return T.new_empty(shape, dtype=torch.float32), T.new_empty(shape, dtype=torch.int32)
+
+
 def register():
     """Define the `rnnpose` operator library and attach the HIP kernels (CUDA dispatch key) and fake implementations."""
     global _lib
@@ -138,7 +154,7 @@ def register():
              "convex_upsample": (_convex_upsample, _f_convex_upsample), "induced_flow": (_induced_flow, _f_induced_flow),
              "corr_weight": (_corr_weight, _f_corr_weight), "lm_normal_eq": (_lm_normal_eq, _f_lm_normal_eq),
              "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step),
-             "zoom_crop": (_zoom_crop, _f_zoom_crop)}
+             "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

@@ -11,7 +11,14 @@ The two are timed alternately inside every run.  The parts are timed the same wa
 / once), the two zoom crops of the three outer iterations (B = 1 plain launches per object / one indexed launch per map), and the
 PoseRefiner call with the descriptors given; "refinement" is that call without its crops.  The frame's image and descriptor map
 live on the device throughout (a camera pipeline hands them over there), so no timing contains a host-to-device copy of them.
-Objects: ellipsoids of 2562 vertices / 5120 faces with hash-generated 256 + 32 vertex features, 3 x 4 schedule, random weights."""
+Objects: ellipsoids of 2562 vertices / 5120 faces with hash-generated 256 + 32 vertex features, 3 x 4 schedule, random weights.
+
+    python tools/scene_bench.py --occlusion [--out profiles/scene_bench_occlusion.json]
+
+measures the occlusion mask between the objects of the frame instead (PoseRefiner(occlusion="frame")): `refine_frame` with and
+without the mask, alternating inside every run, on the same frame; and, at the 240 x 240 crops of the initial poses, the occlusion
+entry point alone (rnnpose_raster_occlusion_f32, all ordered pairs) next to one own render of the batch (rnnpose_raster_mesh_f32 +
+resolve with the resident tables).  Nothing is compared against a threshold."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +58,44 @@ def time_alternately(fns, runs, warmup):
     return {k: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for k, v in ts.items()}
 
 
+def occlusion_bench(a, models, cfg, net, hip, items, given, size, cover):
+    """--occlusion: refine_frame without (the parent's behaviour) and with the mask; the pass and one own render alone"""
+    from rnnpose_amd import zoom
+    n, zs = len(items), tuple(cfg.zoom_crop_size)
+    hip_on = ee.HipEpoch(models, cfg=cfg, desc2d=net, occlusion="frame")
+    hip_on.refiner.load_state_dict(hip.refiner.state_dict())
+    whole = time_alternately({"off": lambda: hip.refine_frame(given), "on": lambda: hip_on.refine_frame(given)}, a.runs, a.warmup)
+    ren, names = hip_on.renderer, [it.class_name for it in items]
+    T0 = torch.as_tensor(np.stack([it.pose_init for it in items]).astype(np.float32)).cuda()
+    K = torch.as_tensor(np.stack([it.K for it in items]).astype(np.float32)).cuda()
+    pc = ren.render_pointcloud(names, T=T0, K=K, render_image_size=size)
+    _, K_crop, _ = zoom.gen_zoom_crop_grids(pc, K, T0, [n, 1, *zs], margin_ratio=0.4, want_grids=False)
+    pairs = ops.OcclusionPairs([0] * n, n, "cuda")
+    bt = ren._batch(names)
+    keys = ren._raster(bt, T0, K_crop, zs, 0.1, perspective=True)
+    geom = (ren.verts, ren.faces, bt["vert_off"], bt["face_off"], bt["face_cnt"], bt["max_faces"], T0, K_crop, zs, pairs)
+    vis, occ = ops.raster_occlusion(*geom, own_keys=keys)
+    own = keys.view(n, -1) != -1
+    alone = time_alternately({"occlusion_pass": lambda: ops.raster_occlusion(*geom, own_keys=keys),
+                              "own_render": lambda: ren(names, None, T=T0, K=K_crop, render_image_size=zs, render_tex=True)}, a.runs, a.warmup)
+    med = lambda r, k: r[k]["median_ms"]
+    added = med(whole, "on") - med(whole, "off")
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=list(size), crop=list(zs), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               verts_per_object=int(next(iter(models.values())).verts.shape[0]), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               pairs=len(pairs), refine_frame=whole, added_ms=added, added_share=added / med(whole, "off"), alone_at_initial_poses=alone,
+               pass_over_own_render=med(alone, "occlusion_pass") / med(alone, "own_render"),
+               own_pixels=int(own.sum()), hidden_pixels=int((occ >= 0).sum()), hidden_share_of_own=float((occ >= 0).sum()) / max(1, int(own.sum())),
+               note="refine_frame off = the parent's behaviour, timed alternately with on in every run; occlusion_pass = the entry point "
+                    "alone (clear + occluder pass + apply) on precomputed own keys; own_render = rnnpose_raster_mesh_f32 + resolve of the "
+                    "same batch; nothing is compared against a threshold")
+    print(f"refine_frame off {med(whole, 'off'):8.2f} ms   on {med(whole, 'on'):8.2f} ms   added {added:+.3f} ms ({res['added_share']:+.2%})")
+    print(f"  at {zs[0]} x {zs[1]}, {len(pairs)} pairs: occlusion pass {med(alone, 'occlusion_pass'):.4f} ms   own render {med(alone, 'own_render'):.4f} ms   "
+          f"hidden {res['hidden_pixels']} of {res['own_pixels']} own pixels")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=8)
@@ -59,6 +104,7 @@ def main():
     ap.add_argument("--size", default="480,640")
     ap.add_argument("--sub", type=int, default=4, help="icosphere subdivisions of the object meshes (4: 2562 vertices)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--occlusion", action="store_true", help="measure the occlusion mask between the objects instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -74,6 +120,8 @@ def main():
     mk = lambda it, g2: ee.EvalItem(it.class_name, image_dev, it.K, it.pose_init, it.pose_gt, g2, frame_id=it.frame_id)
     given, bare = [mk(it, g2_dev) for it in items], [mk(it, None) for it in items]
     cover = float((items[0].image.sum(0) > 0).float().mean())
+    if a.occlusion:
+        return occlusion_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
     per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
     whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
