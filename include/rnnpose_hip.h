@@ -559,6 +559,39 @@ size_t rnnpose_pose_metrics_workspace_bytes(int B, int P);
 int rnnpose_pose_metrics_f64(const float* model, int P, const float* pose_pred, const float* pose_gt, const float* K, int B,
                              int symmetric, void* workspace, size_t workspace_bytes, double* out, rnnpose_stream_t stream);
 
+/* ---- BOP pose-error functions: MSSD / MSPD and VSD (Hodan et al., "BOP challenge 2020 on 6D object localization") -------------
+ * The reference has no code for them and bop_toolkit is absent here: the definitions below are the specification (restated in
+ * fp64 numpy by tests/bop_ref.py); PARITY WITH bop_toolkit IS UNPINNED.  All arithmetic is fp64 on values converted from the fp32
+ * inputs, without fma contraction.  A pose is (3,4) [R|t]; proj(X) = (fx X/Z + cx, fy Y/Z + cy) with K (3,3) row-major.
+ * rnnpose_bop_sym_dist_f64: model (P,3), sym (S,3,4) symmetry transformations, S >= 1 (no symmetry = the identity), pose_est /
+ *   pose_gt (B,3,4), K (B,3,3), all device fp32 -> out (B,2) fp64:
+ *     out[b][0] = MSSD = min_s max_i | T_est x_i - T_gt (S_s x_i) |_2
+ *     out[b][1] = MSPD = min_s max_i | proj(T_est x_i) - proj(T_gt (S_s x_i)) |_2      with K[b]
+ *   T_gt S_s is formed first (fp64), then applied.  workspace: (B,S,2) fp64 partial maxima.  Two launches, no atomics.
+ * rnnpose_bop_vsd_f64: depth_est / depth_gt (B,H,W) fp32 z-buffer depths of the model under the two poses, depth_obs (S_obs,H,W)
+ *   fp32 observed depth, sample b reads depth_obs[src_index[b]] (device int32, B entries), K (B,3,3), diameter (B) device fp32
+ *   (> 0: distances are divided by it; <= 0: left as they are), delta and taus[NT] HOST values (1 <= NT <= 16; copied into the
+ *   launch arguments, nothing is read from `taus` after the call returns).
+ *   A model depth d is EMPTY where !(d > 0) (0, -1, NaN); an observed depth is MISSING where !(d > 0) or it is not finite.
+ *   dist = d * sqrt(((u - cx)/fx)^2 + ((v - cy)/fy)^2 + 1) at integer pixel indices u in [0,W), v in [0,H), no half-pixel offset.
+ *     vis(m)  = !empty(m) && (missing(obs) || dist_m - dist_obs <= delta)
+ *     vis_gt  = vis(gt);   vis_est = vis(est) || (vis_gt && !empty(est));   inter = vis_gt && vis_est;   union = vis_gt || vis_est
+ *     e = |dist_gt - dist_est| on inter pixels ( / diameter when normalising);   n_tau = #{inter: e >= tau}
+ *     err_tau = (n_tau + #union - #inter) / #union,   1.0 when #union == 0
+ *   counts (B, 2+NT) int64 = [#union, #inter, n_tau...], err (B,NT) fp64.  THE CALLER checks the index range on the host
+ *   (rnnpose_amd.ops.bop_vsd does); a sample whose index is outside [0,S_obs) reads nothing: zero counts, NaN errors, and the call
+ *   still returns 0.  workspace: one int32 record of 2+NT counters per workgroup of 2048 pixels.  Two launches, no atomics:
+ *   results are bit-identical from run to run and independent of B.
+ * Both: a null pointer, a bad size, NT > 16, S < 1 or a short workspace return 1 and launch nothing; no allocation, no
+ *   synchronisation. */
+size_t rnnpose_bop_sym_dist_workspace_bytes(int B, int S);
+int rnnpose_bop_sym_dist_f64(const float* model, int P, const float* sym, int S, const float* pose_est, const float* pose_gt,
+                             const float* K, int B, void* workspace, size_t workspace_bytes, double* out, rnnpose_stream_t stream);
+size_t rnnpose_bop_vsd_workspace_bytes(int B, int H, int W, int NT);
+int rnnpose_bop_vsd_f64(const float* depth_est, const float* depth_gt, const float* depth_obs, int S_obs, const int* src_index,
+                        const float* K, const float* diameter, int B, int H, int W, double delta, const double* taus, int NT,
+                        void* workspace, size_t workspace_bytes, long long* counts, double* err, rnnpose_stream_t stream);
+
 /* ---- f4 ("next"): zoom-crop of every outer iteration on device ------- model/PoseRefiner.py:145-218,286-291
  * mask_bbox: bbox (B,4) int32 = [xmin, ymin, xmax, ymax] of depth (B,1,H,W) > 0 ([INT_MAX,INT_MAX,-1,-1] if empty).
  * zoom_crop_params: get_affine_transformation + gen_zoom_crop_grids without the host round trip: K (B,3,3), T (B,4,4)

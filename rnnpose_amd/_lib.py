@@ -146,6 +146,10 @@ PROTOTYPES = {
     "rnnpose_raster_occlusion_f32": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _f, _p, _p, _i, _f, _p, _p, _z, _p, _p, _p, _p]),
     "rnnpose_pose_metrics_workspace_bytes": (_z, [_i, _i]),
     "rnnpose_pose_metrics_f64": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _z, _p, _p]),
+    "rnnpose_bop_sym_dist_workspace_bytes": (_z, [_i, _i]),
+    "rnnpose_bop_sym_dist_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _z, _p, _p]),
+    "rnnpose_bop_vsd_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "rnnpose_bop_vsd_f64": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _d, _p, _i, _p, _z, _p, _p, _p]),
 }
 
 _lib = None

@@ -147,6 +147,174 @@ __global__ __launch_bounds__(256) void pose_metrics_kernel(const float* __restri
   }
 }
 
+// max over the workgroup with a NaN that sticks (np.max semantics): the shape of block_sum
+__device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
+__device__ __forceinline__ double block_max(double v, double* red) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_down(lo, d);
+    hi = __shfl_down(hi, d);
+    v = nan_max(v, __hiloint2double(hi, lo));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  double m = red[0];
+  for (int w = 1; w < 4; ++w) m = nan_max(m, red[w]);
+  return m;
+}
+
+// ---- BOP pose-error functions (Hodan et al., BOP challenge 2019/2020): MSSD / MSPD and VSD -----------------------------------
+// MSSD = min_s max_i |T_est x_i - T_gt S_s x_i|, MSPD the same with both points projected by the sample's K.
+// One workgroup per (s, b): T_gt S_s is formed once (12 threads -> LDS), the threads stride over the P model points, block max of
+// both distances -> partial (B,S,2).  No atomics: bop_sym_min_kernel takes the min over S.
+__global__ __launch_bounds__(256) void bop_sym_dist_kernel(const float* __restrict__ model, int P, const float* __restrict__ sym, int S,
+                                                           const float* __restrict__ pose_est, const float* __restrict__ pose_gt,
+                                                           const float* __restrict__ K, double* __restrict__ partial) {
+  __shared__ double M[12];
+  __shared__ double red[4];
+  const int s = blockIdx.x, b = blockIdx.y;
+  const float* Te = pose_est + 12 * b;
+  if (threadIdx.x < 12) {
+    const float* Tg = pose_gt + 12 * b;
+    const float* Ss = sym + 12 * static_cast<long long>(s);
+    const int r = threadIdx.x >> 2, c = threadIdx.x & 3;
+    double v = static_cast<double>(Tg[4 * r]) * Ss[c] + static_cast<double>(Tg[4 * r + 1]) * Ss[4 + c] + static_cast<double>(Tg[4 * r + 2]) * Ss[8 + c];
+    if (c == 3) v = v + static_cast<double>(Tg[4 * r + 3]);
+    M[threadIdx.x] = v;
+  }
+  __syncthreads();
+  const double fx = K[9 * b], cx = K[9 * b + 2], fy = K[9 * b + 4], cy = K[9 * b + 5];
+  double m3 = 0.0, m2 = 0.0;
+  for (int i = threadIdx.x; i < P; i += 256) {
+    const double x = model[3 * i], y = model[3 * i + 1], z = model[3 * i + 2];
+    double pe[3], pg[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      pe[r] = static_cast<double>(Te[4 * r]) * x + static_cast<double>(Te[4 * r + 1]) * y + static_cast<double>(Te[4 * r + 2]) * z + static_cast<double>(Te[4 * r + 3]);
+      pg[r] = M[4 * r] * x + M[4 * r + 1] * y + M[4 * r + 2] * z + M[4 * r + 3];
+    }
+    const double dx = pe[0] - pg[0], dy = pe[1] - pg[1], dz = pe[2] - pg[2];
+    m3 = nan_max(m3, sqrt(dx * dx + dy * dy + dz * dz));
+    const double ex = (fx * pe[0] / pe[2] + cx) - (fx * pg[0] / pg[2] + cx), ey = (fy * pe[1] / pe[2] + cy) - (fy * pg[1] / pg[2] + cy);
+    m2 = nan_max(m2, sqrt(ex * ex + ey * ey));
+  }
+  m3 = block_max(m3, red);
+  m2 = block_max(m2, red);
+  if (threadIdx.x == 0) {
+    double* o = partial + (static_cast<long long>(b) * S + s) * 2;
+    o[0] = m3;
+    o[1] = m2;
+  }
+}
+
+__global__ __launch_bounds__(256) void bop_sym_min_kernel(const double* __restrict__ partial, int B, int S, double* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const double* p = partial + static_cast<long long>(b) * S * 2;
+  double m3 = p[0], m2 = p[1];
+  for (int s = 1; s < S; ++s) {
+    const double a = p[2 * s], c = p[2 * s + 1];
+    m3 = (a < m3 || a != a) ? a : m3;
+    m2 = (c < m2 || c != c) ? c : m2;
+  }
+  out[2 * b] = m3;
+  out[2 * b + 1] = m2;
+}
+
+// VSD.  Every workgroup takes BOP_TILE consecutive pixels of one sample: pixel = tile start + k * 256 + thread, so the lanes of a
+// wave read 64 consecutive floats of each of the three depth images.  Per thread 2 + NT int32 counters [union, inter, n_tau...],
+// reduced by wave shuffles, then LDS, then ONE partial record per workgroup; bop_vsd_finalize_kernel sums the records in int64.
+constexpr int BOP_TILE = 2048;
+constexpr int BOP_MAX_NT = 16;
+constexpr int BOP_NC = 2 + BOP_MAX_NT;
+
+struct BopTaus {
+  double v[BOP_MAX_NT];
+};
+
+__global__ __launch_bounds__(256) void bop_vsd_kernel(const float* __restrict__ depth_est, const float* __restrict__ depth_gt,
+                                                      const float* __restrict__ depth_obs, int S_obs, const int* __restrict__ src_index,
+                                                      const float* __restrict__ K, const float* __restrict__ diameter, int H, int W,
+                                                      double delta, BopTaus taus, int NT, int* __restrict__ partial) {
+  __shared__ int red[4][BOP_NC];
+  const int b = blockIdx.y;
+  const int src = src_index[b];
+  const int HW = H * W;
+  int cnt[BOP_NC];
+#pragma unroll
+  for (int c = 0; c < BOP_NC; ++c) cnt[c] = 0;
+  if (src >= 0 && src < S_obs) {          // (a sample whose index is out of range counts nothing: the finalize writes NaN errors)
+    const float* pe = depth_est + static_cast<long long>(b) * HW;
+    const float* pg = depth_gt + static_cast<long long>(b) * HW;
+    const float* po = depth_obs + static_cast<long long>(src) * HW;
+    const double fx = K[9 * b], cx = K[9 * b + 2], fy = K[9 * b + 4], cy = K[9 * b + 5];
+    const double diam = diameter[b];
+    const bool normalise = diam > 0.0;
+    const int p0 = blockIdx.x * BOP_TILE + threadIdx.x;
+    for (int k = 0; k < BOP_TILE / 256; ++k) {
+      const int p = p0 + k * 256;
+      if (p >= HW) break;
+      const float fe = pe[p], fg = pg[p], fo = po[p];
+      const int v = p / W, u = p - v * W;
+      const double rx = (u - cx) / fx, ry = (v - cy) / fy;
+      const double ray = sqrt(rx * rx + ry * ry + 1.0);
+      const double de = static_cast<double>(fe) * ray, dg = static_cast<double>(fg) * ray, dob = static_cast<double>(fo) * ray;
+      const bool empty_e = !(fe > 0.f), empty_g = !(fg > 0.f);
+      const bool missing = !(fo > 0.f) || !(fabsf(fo) <= FLT_MAX);
+      const bool vis_g = !empty_g && (missing || dg - dob <= delta);
+      const bool vis_e = (!empty_e && (missing || de - dob <= delta)) || (vis_g && !empty_e);
+      const bool inter = vis_g && vis_e;
+      cnt[0] += (vis_g || vis_e) ? 1 : 0;
+      cnt[1] += inter ? 1 : 0;
+      double e = fabs(dg - de);
+      if (normalise) e = e / diam;
+#pragma unroll
+      for (int t = 0; t < BOP_MAX_NT; ++t) cnt[2 + t] += (t < NT && inter && e >= taus.v[t]) ? 1 : 0;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < BOP_NC; ++c) {
+    int x = cnt[c];
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
+    if (lane == 0) red[wave][c] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 + NT)
+    partial[(static_cast<long long>(b) * gridDim.x + blockIdx.x) * (2 + NT) + threadIdx.x] =
+        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// one workgroup per sample: thread c < 2 + NT sums counter c over the sample's records (int64), then err_tau of the definitions
+__global__ __launch_bounds__(64) void bop_vsd_finalize_kernel(const int* __restrict__ partial, int nblk, int S_obs,
+                                                              const int* __restrict__ src_index, int NT, long long* __restrict__ counts,
+                                                              double* __restrict__ err) {
+  __shared__ long long tot[BOP_NC];
+  const int b = blockIdx.x, c = threadIdx.x;
+  const int src = src_index[b];
+  const bool ok = src >= 0 && src < S_obs;
+  if (c < 2 + NT) {
+    long long s = 0;
+    const int* p = partial + static_cast<long long>(b) * nblk * (2 + NT) + c;
+    if (ok)
+      for (int k = 0; k < nblk; ++k) s += p[static_cast<long long>(k) * (2 + NT)];
+    tot[c] = s;
+    counts[static_cast<long long>(b) * (2 + NT) + c] = s;
+  }
+  __syncthreads();
+  if (c < NT) {
+    double e = 1.0;
+    if (!ok)
+      e = __longlong_as_double(0x7ff8000000000000ll);
+    else if (tot[0] > 0)
+      e = static_cast<double>(tot[2 + c] + tot[0] - tot[1]) / static_cast<double>(tot[0]);
+    err[static_cast<long long>(b) * NT + c] = e;
+  }
+}
+
 int launch_nn(const float* ref, const float* que, int* idxs, int b, int pn1, int pn2, int dim, int exclude_self,
               hipStream_t st) {
   dim3 grid(rp::cdiv(pn2, 256), b), block(256);
@@ -193,6 +361,49 @@ int rnnpose_pose_metrics_f64(const float* model, int P, const float* pose_pred, 
     launch_nn(pp, pg, idx, B, P, P, 3, 0, st);      // ref = predicted points, queries = target points
   }
   hipLaunchKernelGGL(pose_metrics_kernel, dim3(B), dim3(256), 0, st, model, P, pose_pred, pose_gt, K, pp, pg, idx, out);
+  return rp::check_launch(fn);
+}
+
+size_t rnnpose_bop_sym_dist_workspace_bytes(int B, int S) {
+  if (B <= 0 || S <= 0) return 0;
+  return static_cast<size_t>(B) * S * 2 * sizeof(double);
+}
+
+int rnnpose_bop_sym_dist_f64(const float* model, int P, const float* sym, int S, const float* pose_est, const float* pose_gt,
+                             const float* K, int B, void* workspace, size_t workspace_bytes, double* out, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_bop_sym_dist_f64";
+  RP_REQUIRE(model && sym && pose_est && pose_gt && K && workspace && out, fn, "null pointer");
+  RP_REQUIRE(S >= 1, fn, "S < 1: an object without symmetries passes the identity");
+  RP_REQUIRE(B > 0 && B < 65536 && P > 0, fn, "bad size");
+  RP_REQUIRE(workspace_bytes >= rnnpose_bop_sym_dist_workspace_bytes(B, S), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  double* partial = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(bop_sym_dist_kernel, dim3(S, B), dim3(256), 0, st, model, P, sym, S, pose_est, pose_gt, K, partial);
+  hipLaunchKernelGGL(bop_sym_min_kernel, dim3(rp::cdiv(B, 256)), dim3(256), 0, st, partial, B, S, out);
+  return rp::check_launch(fn);
+}
+
+size_t rnnpose_bop_vsd_workspace_bytes(int B, int H, int W, int NT) {
+  if (B <= 0 || H <= 0 || W <= 0 || NT < 1 || NT > BOP_MAX_NT || static_cast<long long>(H) * W > 0x7fffffffll - BOP_TILE) return 0;
+  return static_cast<size_t>(B) * rp::cdiv(static_cast<long long>(H) * W, BOP_TILE) * (2 + NT) * sizeof(int);
+}
+
+int rnnpose_bop_vsd_f64(const float* depth_est, const float* depth_gt, const float* depth_obs, int S_obs, const int* src_index,
+                        const float* K, const float* diameter, int B, int H, int W, double delta, const double* taus, int NT,
+                        void* workspace, size_t workspace_bytes, long long* counts, double* err, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_bop_vsd_f64";
+  RP_REQUIRE(depth_est && depth_gt && depth_obs && src_index && K && diameter && taus && workspace && counts && err, fn, "null pointer");
+  RP_REQUIRE(NT >= 1 && NT <= BOP_MAX_NT, fn, "NT must lie in [1, 16]");
+  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && S_obs > 0 && static_cast<long long>(H) * W <= 0x7fffffffll - BOP_TILE, fn, "bad size");
+  RP_REQUIRE(workspace_bytes >= rnnpose_bop_vsd_workspace_bytes(B, H, W, NT), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  BopTaus tv;
+  for (int t = 0; t < BOP_MAX_NT; ++t) tv.v[t] = t < NT ? taus[t] : 0.0;
+  const int nblk = rp::cdiv(static_cast<long long>(H) * W, BOP_TILE);
+  int* partial = static_cast<int*>(workspace);
+  hipLaunchKernelGGL(bop_vsd_kernel, dim3(nblk, B), dim3(256), 0, st, depth_est, depth_gt, depth_obs, S_obs, src_index, K, diameter, H, W,
+                     delta, tv, NT, partial);
+  hipLaunchKernelGGL(bop_vsd_finalize_kernel, dim3(B), dim3(64), 0, st, static_cast<const int*>(partial), nblk, S_obs, src_index, NT, counts, err);
   return rp::check_launch(fn);
 }
 

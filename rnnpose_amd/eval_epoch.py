@@ -42,6 +42,7 @@ class ClassModel:
     verts_uvs: np.ndarray = None     # (U,2) texture coordinates of a textured model (mesh_io.load_obj), else None
     faces_uvs: np.ndarray = None     # (F,3) int32 uv rows of each face
     texture: np.ndarray = None       # (Ht,Wt,3) float32 in [0,1], the class's texture map
+    symmetries: np.ndarray = None    # (S,4,4) symmetry transformations of the BOP errors, identity included (None: no symmetry)
 
 
 @dataclass
@@ -54,6 +55,7 @@ class EvalItem:
     pose_gt: np.ndarray          # (4,4)
     geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image (None: HipEpoch(desc2d=...) computes them)
     frame_id: int | None = None  # camera frame the object was seen in: items of one frame share `image` / `geofea_2d` (None: its own)
+    depth: torch.Tensor | None = None   # (H,W) observed depth of the frame in the meshes' unit, 0 = missing; shared like `image` (BOP VSD)
 
 
 class PackedEpochMetrics:
@@ -112,7 +114,8 @@ def flags_from_metrics(m, diameter, symmetric):
                      (m[:, 3] < 5.0) & (m[:, 4] < 5.0)], 1).astype(np.float64)
 
 
-def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8, symmetric=(), reduce_device=None, group="class"):
+def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8, symmetric=(), reduce_device=None, group="class",
+              bop_fn=None):
     """items: list[EvalItem]; models: {class: ClassModel};
     refine_fn(class_name, [EvalItem]) -> (B,4,4) refined poses (numpy or tensor): one PoseRefiner call per batch;
     metric_fn(class_name, pose_pred (B,4,4), pose_gt (B,4,4)) -> (B,5) [ADD, ADD-S, proj2d, t cm, r deg].
@@ -121,12 +124,19 @@ def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8
     behind `lambda _, batch: epoch.refine_frame(batch)`) and every item's metrics are booked under its own class, with that
     class's diameter and symmetry.
     -> {"init": {cls: {metric: mean, "n": count}}, "refined": {...}} identical on every rank (wrap-around duplicates of the
-    sampler are excluded from the sums)."""
+    sampler are excluded from the sums).
+    bop_fn(batch [EvalItem], poses (B,4,4)) -> (B,3) per-sample recalls [AR_VSD, AR_MSSD, AR_MSPD] (HipEpoch.bop_metrics): the
+    result gains "bop": {"init" | "refined": {cls: {"ar_vsd", "ar_mssd", "ar_mspd", "ar", "n"}, "all": {...}}} from one more
+    all_reduce of a (2 x classes x 4) fp64 buffer.  None (the default): no such entry and no such collective."""
     if group not in ("class", "frame"):
         raise ValueError(f"group must be 'class' or 'frame', got {group!r}")
     classes = sorted(models)
     idx, uniq = D.shard_indices(len(items), rank, world)
     acc = PackedEpochMetrics(classes)
+    bop = None
+    if bop_fn is not None:
+        from .evaluator import BOPAccumulator
+        bop = BOPAccumulator(tuple(f"{k}/{c}" for k in ("init", "refined") for c in classes))
     batches = class_batches(items, idx, uniq, batch_size) if group == "class" else frame_batches(items, idx, uniq, batch_size)
     for cls, ids, us in batches:
         batch = [items[i] for i in ids]
@@ -142,7 +152,22 @@ def run_epoch(items, models, refine_fn, metric_fn, rank=0, world=1, batch_size=8
                 fl = flags_from_metrics(metric_fn(c, poses[rows], gt[rows]), models[c].diameter, sym)
                 for row, j in zip(fl, rows):
                     which.update(c, dict(zip(METRICS, row)), unique=us[j])
-    return acc.reduce(device=reduce_device)
+        if bop is not None:
+            for which, poses in (("init", init), ("refined", pred)):
+                rec = np.asarray(bop_fn(batch, poses), dtype=np.float64).reshape(len(batch), 3)
+                for j, it in enumerate(batch):
+                    bop.update(f"{which}/{it.class_name}", rec[j], unique=us[j])
+    result = acc.reduce(device=reduce_device)
+    if bop is not None:
+        r = bop.reduce(device=reduce_device)
+        result["bop"] = {}
+        for k in ("init", "refined"):
+            per = {c: r[f"{k}/{c}"] for c in classes}
+            n = sum(v["n"] for v in per.values())
+            tot = [sum(v[m] * v["n"] for v in per.values() if v["n"]) / n if n else float("nan") for m in ("ar_vsd", "ar_mssd", "ar_mspd")]
+            per["all"] = {"ar_vsd": tot[0], "ar_mssd": tot[1], "ar_mspd": tot[2], "ar": sum(tot) / 3.0, "n": n}
+            result["bop"][k] = per
+    return result
 
 
 # ---- the GPU pieces behind refine_fn / metric_fn ---------------------------------------------------------------------
@@ -178,6 +203,7 @@ class HipEpoch:
                                                device=device) for n, m in models.items()}
         for n, e in self.evaluators.items():
             e.symmetric = n in self.symmetric
+        self.bop = None                   # bop_metrics: the BOPEvaluator, made on its first call
 
     def refine(self, cls, batch):
         from .transformation import SE3Sequence
@@ -244,6 +270,30 @@ class HipEpoch:
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=fea, Tj_gt=SE3Sequence(matrix=Tg[:, None]),
                            obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index)
         return out["Ti_pred"].G.reshape(-1, 4, 4)
+
+    def bop_metrics(self, batch, pose_pred, want_errors=False):
+        """BOP recalls of the poses `pose_pred` (B,4,4) of the items of `batch` (any classes, one or several camera frames):
+        -> (B,3) fp64 numpy [AR_VSD, AR_MSSD, AR_MSPD] per item  [, the error dictionary of BOPEvaluator.errors].
+        The observed depth (EvalItem.depth) is held once per distinct frame, as refine_frame holds the image, and every item
+        reads its frame's through a source index; an item without a frame id is its own frame.  The bop_fn of run_epoch."""
+        from .evaluator import BOPEvaluator
+        if self.bop is None:
+            self.bop = BOPEvaluator(self.renderer, self.models, device=self.device)
+        src, index = {}, []
+        for j, it in enumerate(batch):
+            if it.depth is None:
+                raise ValueError("bop_metrics: every item needs the observed depth of its frame (EvalItem.depth)")
+            key = ("frame", it.frame_id) if it.frame_id is not None else ("item", j)
+            index.append(src.setdefault(key, (len(src), it))[0])
+        firsts = [it for _, it in sorted(src.values(), key=lambda v: v[0])]
+        depth = torch.stack([it.depth for it in firsts]).to(self.device)
+        names = [it.class_name for it in batch]
+        K = np.stack([it.K for it in batch]).astype(np.float32)
+        gt = np.stack([it.pose_gt for it in batch]).astype(np.float32)
+        pred = pose_pred if torch.is_tensor(pose_pred) else np.asarray(pose_pred, dtype=np.float32)
+        err = self.bop.errors(names, pred, gt, K, depth, src_index=index)
+        rec = self.bop.recalls(err, [self.models[n].diameter for n in names], depth.shape[-1])
+        return (rec, err) if want_errors else rec
 
     def metrics(self, cls, pose_pred, pose_gt):
         ev = self.evaluators[cls]
@@ -340,7 +390,8 @@ def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640),
     image positions and depths: every object is rendered at its ground-truth pose by `renderer` (MeshRenderer) and the frame is
     composed by nearest depth in torch -- colour and rendered descriptors alike -- so nearer objects occlude farther ones.
     Every object becomes an EvalItem that SHARES the frame's image and geofea_2d tensors and carries its frame_id; items of a
-    frame are consecutive.  renderer=None (CPU): hash noise per frame instead of a render."""
+    frame are consecutive, and `depth`, the composed nearest depth (0 on the background): the frame's observed depth for the BOP VSD.
+    renderer=None (CPU): hash noise per frame instead of a render, and no depth."""
     from . import synthetic as syn
     from .evaluator import LINEMOD_K
     H, W = image_size
@@ -377,7 +428,10 @@ def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640),
             comp = torch.gather(out, 0, near.expand(1, out.shape[1], H, W))[0]
             comp = comp * torch.isfinite(z.min(0).values).to(comp.dtype)                     # background stays 0
             image, g2 = (comp[:3] * 255.0).cpu(), comp[3:].cpu()
+            zmin = z.min(0).values[0]                                                        # the frame's observed depth, 0 = background
+            obs = torch.where(torch.isfinite(zmin), zmin, torch.zeros_like(zmin)).cpu()
         for it in frame:
             it.image, it.geofea_2d = image, g2
+            it.depth = obs if renderer is not None else None
         items += frame
     return items

@@ -1495,6 +1495,83 @@ def pose_metrics(model, pose_pred, pose_gt, K, symmetric: bool = False):
     return out
 
 
+# ---- BOP pose-error functions (MSSD / MSPD / VSD; definitions in include/rnnpose_hip.h) ----------------------------------
+BOP_MAX_TAUS = 16
+
+
+def bop_sym_dist(model, sym, pose_est, pose_gt, K):
+    """model (P,3), sym (S,3,4) symmetry transformations (S >= 1; the identity for an object without symmetries), pose_est /
+    pose_gt (B,3,4), K (3,3) or (B,3,3) -> (B,2) fp64 [MSSD, MSPD px]: min over the symmetries of the max over the model points
+    of the 3-D distance / of the distance of the projections (rnnpose_bop_sym_dist_f64).  Shapes are checked here (ValueError)."""
+    model, sym, pose_est, pose_gt, K = _chk(model, "model"), _chk(sym, "sym"), _chk(pose_est, "pose_est"), _chk(pose_gt, "pose_gt"), \
+        _chk(K, "K")
+    if model.dim() != 2 or model.shape[1] != 3 or model.shape[0] < 1:
+        raise ValueError(f"bop_sym_dist: model must be (P,3) with P >= 1, got {tuple(model.shape)}")
+    if sym.dim() != 3 or sym.shape[1:] != (3, 4) or sym.shape[0] < 1:
+        raise ValueError(f"bop_sym_dist: sym must be (S,3,4) with S >= 1, got {tuple(sym.shape)}")
+    if pose_est.dim() != 3 or pose_est.shape[1:] != (3, 4) or pose_gt.shape != pose_est.shape or pose_est.shape[0] < 1:
+        raise ValueError(f"bop_sym_dist: pose_est and pose_gt must both be (B,3,4), got {tuple(pose_est.shape)} and {tuple(pose_gt.shape)}")
+    P, S, B = model.shape[0], sym.shape[0], pose_est.shape[0]
+    if K.shape == (3, 3):
+        K = K.expand(B, 3, 3).contiguous()
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"bop_sym_dist: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
+    n = int(_lib.load().rnnpose_bop_sym_dist_workspace_bytes(B, S))
+    ws = torch.empty(n // 8, device=model.device, dtype=F64)
+    out = torch.empty(B, 2, device=model.device, dtype=F64)
+    _launch("rnnpose_bop_sym_dist_f64", _ptr(model), P, _ptr(sym), S, _ptr(pose_est), _ptr(pose_gt), _ptr(K), B, _ptr(ws), n, _ptr(out),
+            _stream())
+    return out
+
+
+def bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus):
+    """Visible surface discrepancy.  depth_est / depth_gt (B,H,W) fp32: z-buffer depths of the model under the two poses (empty
+    where not > 0); depth_obs (S,H,W) fp32 observed depth (missing where not > 0 or not finite); src_index: an ops.SourceIndex, B
+    integers (tensor / sequence) or None (= sample b reads depth_obs[b]); K (3,3) or (B,3,3); diameter: a number or B values (> 0
+    normalises the distances, <= 0 leaves them); delta a number; taus 1..16 numbers (host values).
+    -> err (B,NT) fp64, counts (B, 2+NT) int64 [#union, #inter, n_tau...]   (rnnpose_bop_vsd_f64).
+    Shapes, NT and the index range are checked here, on the host (ValueError); nothing is launched then."""
+    depth_est, depth_gt, depth_obs, K = _chk(depth_est, "depth_est"), _chk(depth_gt, "depth_gt"), _chk(depth_obs, "depth_obs"), _chk(K, "K")
+    taus = [float(t) for t in (taus.detach().cpu().tolist() if isinstance(taus, torch.Tensor) else taus)]
+    NT = len(taus)
+    if not 1 <= NT <= BOP_MAX_TAUS:
+        raise ValueError(f"bop_vsd: between 1 and {BOP_MAX_TAUS} taus, got {NT}")
+    if depth_est.dim() != 3 or depth_gt.shape != depth_est.shape or depth_est.numel() == 0:
+        raise ValueError(f"bop_vsd: depth_est and depth_gt must both be (B,H,W), got {tuple(depth_est.shape)} and {tuple(depth_gt.shape)}")
+    B, H, W = depth_est.shape
+    if depth_obs.dim() != 3 or depth_obs.shape[1:] != (H, W) or depth_obs.shape[0] < 1:
+        raise ValueError(f"bop_vsd: depth_obs must be (S,{H},{W}), got {tuple(depth_obs.shape)}")
+    S = depth_obs.shape[0]
+    if src_index is None:
+        src_index = range(B)
+    if not isinstance(src_index, SourceIndex):
+        src_index = SourceIndex(src_index, S, depth_est.device)
+    if src_index.S != S or len(src_index) != B:
+        raise ValueError(f"bop_vsd: src_index covers {len(src_index)} samples of {src_index.S} sources; there are {B} samples, {S} sources")
+    if K.shape == (3, 3):
+        K = K.expand(B, 3, 3).contiguous()
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"bop_vsd: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
+    if isinstance(diameter, torch.Tensor):
+        diameter = _chk(diameter.reshape(-1), "diameter")
+    else:
+        diameter = torch.as_tensor(diameter, dtype=F32).reshape(-1).to(depth_est.device)
+    if diameter.numel() == 1:
+        diameter = diameter.expand(B).contiguous()
+    if diameter.numel() != B:
+        raise ValueError(f"bop_vsd: diameter must be a number or {B} values")
+    n = int(_lib.load().rnnpose_bop_vsd_workspace_bytes(B, H, W, NT))
+    if n == 0:
+        raise ValueError(f"bop_vsd: {H} x {W} pixels are more than one call takes")
+    ws = torch.empty(n // 4, device=depth_est.device, dtype=torch.int32)
+    counts = torch.empty(B, 2 + NT, device=depth_est.device, dtype=torch.int64)
+    err = torch.empty(B, NT, device=depth_est.device, dtype=F64)
+    tv = (C.c_double * NT)(*taus)
+    _launch("rnnpose_bop_vsd_f64", _ptr(depth_est), _ptr(depth_gt), _ptr(depth_obs), S, _ptr(src_index.dev), _ptr(K), _ptr(diameter), B, H, W,
+            float(delta), C.cast(tv, C.c_void_p), NT, _ptr(ws), n, _ptr(counts), _ptr(err), _stream())
+    return err, counts
+
+
 # ---- f4: zoom-crop on device ---------------------------------------------------------------------------------------
 def pointcloud_depth(verts, vert_offsets, T, K, size):
     """verts (P,3) fp32 (all models concatenated), vert_offsets (B+1,) int32 device tensor, T (B,4,4), K (B,3,3), size (H,W)

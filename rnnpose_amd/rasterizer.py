@@ -288,6 +288,15 @@ class MeshRenderer:
         ws = self._raster(bt, T, K, render_image_size, near, perspective=pc)
         return self._resolve(bt, T, K, render_image_size, near, pc, ws, want_vdepth=True)[2]
 
+    def render_zbuf(self, model_names, T, K, render_image_size, near=0.1, empty_depth=-1.0):
+        """(B,1,h,w): the z-buffer depth alone -- the interpolated camera z of the nearest face, the depth channel of __call__ without
+        its attribute maps; `empty_depth` (non-positive) where no face covers the pixel.  The depth images of the BOP visible
+        surface discrepancy (evaluator.BOPEvaluator)."""
+        bt = self._batch(model_names)
+        T, K = self._tk(T, K)
+        ws = self._raster(bt, T, K, render_image_size, near, perspective=True)
+        return self._resolve(bt, T, K, render_image_size, near, True, ws, want_zbuf=True, empty_depth=empty_depth)[1]
+
     def _explicit_attr(self, bt, vert_attribute, B):
         if isinstance(vert_attribute, (list, tuple)):
             if len(vert_attribute) < B:

@@ -30,6 +30,8 @@ _SCHEMAS = {
     "lm_solve_update": "(Tensor H, Tensor b, Tensor G, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
     "zoom_crop": "(Tensor x, Tensor theta, int[] crop_size, Tensor? src_index=None) -> Tensor",
     "raster_occlusion": "(Tensor verts, Tensor faces, Tensor vert_off, Tensor face_off, Tensor face_cnt, int max_faces, Tensor T, Tensor K, int[] size, Tensor pair_target, Tensor pair_occluder, float margin=0.0, float near=0.1, float pixel_center=0.5) -> (Tensor visible, Tensor occluder)",
+    "bop_sym_dist": "(Tensor model, Tensor sym, Tensor pose_est, Tensor pose_gt, Tensor K) -> Tensor",
+    "bop_vsd": "(Tensor depth_est, Tensor depth_gt, Tensor depth_obs, Tensor src_index, Tensor K, Tensor diameter, float delta, float[] taus) -> (Tensor err, Tensor counts)",
     "lm_step": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
 }
 
@@ -95,6 +97,15 @@ def _raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, 
                                 pixel_center=pixel_center, want_occluder=True)
 
 
+def _bop_sym_dist(model, sym, pose_est, pose_gt, K):
+    return ops.bop_sym_dist(model, sym, pose_est, pose_gt, K)
+
+
+def _bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus):
+    """src_index: (B,) integer tensor, checked on the host (ValueError) before anything is launched."""
+    return ops.bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus)
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
 def _f_corr_pyramid(fmap1, fmap2, levels=4):
     B, _, h, w = fmap1.shape
@@ -144,6 +155,15 @@ def _f_raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T
     return T.new_empty(shape, dtype=torch.float32), T.new_empty(shape, dtype=torch.int32)
 
 
+def _f_bop_sym_dist(model, sym, pose_est, pose_gt, K):
+    return model.new_empty((pose_est.shape[0], 2), dtype=torch.float64)
+
+
+def _f_bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus):
+    B, NT = depth_est.shape[0], len(taus)
+    return depth_est.new_empty((B, NT), dtype=torch.float64), depth_est.new_empty((B, 2 + NT), dtype=torch.int64)
+
+
 def register():
     """Define the `rnnpose` operator library and attach the HIP kernels (CUDA dispatch key) and fake implementations."""
     global _lib
@@ -154,7 +174,8 @@ def register():
              "convex_upsample": (_convex_upsample, _f_convex_upsample), "induced_flow": (_induced_flow, _f_induced_flow),
              "corr_weight": (_corr_weight, _f_corr_weight), "lm_normal_eq": (_lm_normal_eq, _f_lm_normal_eq),
              "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step),
-             "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion)}
+             "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
+             "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

@@ -18,7 +18,14 @@ Objects: ellipsoids of 2562 vertices / 5120 faces with hash-generated 256 + 32 v
 measures the occlusion mask between the objects of the frame instead (PoseRefiner(occlusion="frame")): `refine_frame` with and
 without the mask, alternating inside every run, on the same frame; and, at the 240 x 240 crops of the initial poses, the occlusion
 entry point alone (rnnpose_raster_occlusion_f32, all ordered pairs) next to one own render of the batch (rnnpose_raster_mesh_f32 +
-resolve with the resident tables).  Nothing is compared against a threshold."""
+resolve with the resident tables).  Nothing is compared against a threshold.
+
+    python tools/scene_bench.py --bop [--out profiles/scene_bench_bop.json]
+
+times the BOP pose-error functions of the frame at its initial poses: `HipEpoch.bop_metrics` (two z-buffer renders of the batch at the
+frame size, rnnpose_bop_vsd_f64, rnnpose_bop_sym_dist_f64 per class, the recalls on the host), `BOPEvaluator.errors` (the same without
+the copy back), the two entry points alone on ready depth images, and -- wall clock, on the host -- their numpy restatement
+tests/bop_ref.py on the same inputs.  Nothing is compared against a threshold."""
 from __future__ import annotations
 
 import argparse
@@ -96,6 +103,59 @@ def occlusion_bench(a, models, cfg, net, hip, items, given, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def bop_bench(a, models, hip, items, size, cover):
+    """--bop: the BOP errors of the frame's objects at their initial poses"""
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bop_ref as br
+    H, W = size
+    n = len(items)
+    depth_dev = items[0].depth.cuda()
+    dev_items = [ee.EvalItem(it.class_name, it.image, it.K, it.pose_init, it.pose_gt, None, frame_id=it.frame_id, depth=depth_dev) for it in items]
+    names = [it.class_name for it in items]
+    init = torch.as_tensor(np.stack([it.pose_init for it in items]).astype(np.float32)).cuda()
+    gt = torch.as_tensor(np.stack([it.pose_gt for it in items]).astype(np.float32)).cuda()
+    K = torch.as_tensor(np.stack([it.K for it in items]).astype(np.float32)).cuda()
+    rec, err = hip.bop_metrics(dev_items, init, want_errors=True)
+    ev = hip.bop
+    idx = ops.SourceIndex([0] * n, 1, "cuda")
+    obs = depth_dev[None].contiguous()
+    d_est = ev.renderer.render_zbuf(names, init, K, (H, W))[:, 0].contiguous()
+    d_gt = ev.renderer.render_zbuf(names, gt, K, (H, W))[:, 0].contiguous()
+    diam = torch.tensor([ev.diameter[c] for c in names], dtype=torch.float32, device="cuda")
+    pe, pg = init[:, :3].contiguous(), gt[:, :3].contiguous()
+
+    def sym_all():
+        for j, c in enumerate(names):
+            ops.bop_sym_dist(ev.points[c], ev.sym[c], pe[j:j + 1], pg[j:j + 1], K[j:j + 1])
+    whole = time_alternately({"bop_metrics": lambda: hip.bop_metrics(dev_items, init),
+                              "errors_on_device": lambda: ev.errors(names, init, gt, K, obs, src_index=idx),
+                              "two_depth_renders": lambda: (ev.renderer.render_zbuf(names, init, K, (H, W)), ev.renderer.render_zbuf(names, gt, K, (H, W))),
+                              "vsd_kernels": lambda: ops.bop_vsd(d_est, d_gt, obs, idx, K, diam, ev.delta, ev.taus),
+                              "sym_dist_kernels": sym_all}, a.runs, a.warmup)
+    h = lambda t: t.detach().cpu().numpy()
+    t0 = time.perf_counter()
+    werr, wcounts, near = br.vsd(h(d_est), h(d_gt), h(obs), [0] * n, h(K), h(diam), ev.delta, ev.taus)
+    t1 = time.perf_counter()
+    wsd = np.concatenate([br.sym_dist(h(ev.points[c]), h(ev.sym[c]), h(pe[j:j + 1]), h(pg[j:j + 1]), h(K[j])) for j, c in enumerate(names)])
+    t2 = time.perf_counter()
+    same = bool(np.array_equal(h(err["counts"]), wcounts)) and bool(np.allclose(np.stack([h(err["mssd"]), h(err["mspd"])], 1), wsd, rtol=1e-6, atol=1e-9))
+    med = lambda k: whole[k]["median_ms"]
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=[H, W], verts_per_object=int(next(iter(models.values())).verts.shape[0]),
+               symmetries_per_object=[int(ev.sym[c].shape[0]) for c in names], taus=len(ev.taus), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               device_ms=whole, numpy_reference_ms=dict(vsd=(t1 - t0) * 1e3, sym_dist=(t2 - t1) * 1e3), equals_reference=same,
+               reference_comparisons_near_a_threshold=int(near), mean_recalls=[float(v) for v in rec.mean(0)],
+               note="bop_metrics = two z-buffer renders at the frame size + both entry points + recalls on the host (one copy back); the kernels "
+                    "alone run on ready depth images; the numpy reference is tests/bop_ref.py, wall clock, one run; nothing is compared "
+                    "against a threshold")
+    print(f"bop_metrics {med('bop_metrics'):.3f} ms  errors on device {med('errors_on_device'):.3f} ms  renders {med('two_depth_renders'):.3f} ms  "
+          f"vsd {med('vsd_kernels'):.4f} ms  sym_dist ({n} calls) {med('sym_dist_kernels'):.4f} ms")
+    print(f"  numpy reference: vsd {(t1 - t0) * 1e3:.1f} ms  sym_dist {(t2 - t1) * 1e3:.1f} ms   equal to it: {same}")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=8)
@@ -105,6 +165,7 @@ def main():
     ap.add_argument("--sub", type=int, default=4, help="icosphere subdivisions of the object meshes (4: 2562 vertices)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--occlusion", action="store_true", help="measure the occlusion mask between the objects instead (see above)")
+    ap.add_argument("--bop", action="store_true", help="time the BOP pose-error functions of the frame instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -120,6 +181,8 @@ def main():
     mk = lambda it, g2: ee.EvalItem(it.class_name, image_dev, it.K, it.pose_init, it.pose_gt, g2, frame_id=it.frame_id)
     given, bare = [mk(it, g2_dev) for it in items], [mk(it, None) for it in items]
     cover = float((items[0].image.sum(0) > 0).float().mean())
+    if a.bop:
+        return bop_bench(a, models, hip, items, (H, W), cover)
     if a.occlusion:
         return occlusion_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
