@@ -167,6 +167,39 @@ int rnnpose_lm_step_io_f32(const float* target, int target_mode, const float* we
                            int num_iters, double ep_lambda, double lm_lambda, double max_update, void* workspace,
                            size_t workspace_bytes, double* Hm, double* bv, float* xi, int* info,
                            rnnpose_stream_t stream);
+/* ---- the depth-aware step (RGB-D): a9 / the fused step with an opt-in 3-D residual from the OBSERVED depth in the same sums.
+ * The 2-D terms (v, w, J, X0, X1 = G X0, the clamped Zc, K, target) are those of rnnpose_lm_normal_eq_f64.  In addition, for a
+ * crop pixel (x, y) with matched position t = (tx, ty) in crop pixel-index coordinates (after target_mode handling):
+ *  1. position in the observed frame, fp32 in this order, theta (B,2,3) the affine map that made the crop (rnnpose_zoom_crop_f32):
+ *     bx = (2 tx + 1)/W - 1, by = (2 ty + 1)/H - 1; gx = th0 bx + th1 by + th2, gy = th3 bx + th4 by + th5;
+ *     ix = ((gx + 1) Wo - 1)/2, iy = ((gy + 1) Ho - 1)/2;
+ *  2. observed depth zo at (ix, iy) from obs_depth[src_index[b]] (S,Ho,Wo); a tap is missing when it is outside the frame, <= 0 or
+ *     not finite.  All four bilinear taps present and max - min <= edge_tol: bilinear (weights and order of the crop kernel);
+ *     otherwise the nearest tap (floor(ix + 0.5), floor(iy + 0.5)) if present; otherwise the pixel has no depth term.  A non-finite
+ *     ix / iy, or one with |.| >= 1e8, has no depth term;
+ *  3. observed point Y = zo K_obs^-1 (ix, iy, 1), K_obs (B,3,3) the FULL-FRAME intrinsics of object b (fx, fy, cx, cy are read);
+ *  4. the term is active iff v holds and |Y.z - X1.z| <= depth_gate (inclusive);
+ *  5. omega = depth_weight fx fy / Zc^2 with the crop's fx, fy, and 0 where Zc <= 0.02 (where the 2-D Jacobian is zeroed);
+ *  6. with r3 = Y - X1 and J_T = [I | -[X1]x]:  Hm += v w omega J_T^T J_T,  bv += v w omega J_T^T r3;
+ *     dstats (B,2) fp64, may be NULL: [b][0] = number of active pixels, [b][1] = sum v w omega |r3|^2.
+ * src_index (B) int32 device pointer, or NULL: S == B and object b reads frame b.  depth_weight = 0, or an observed depth without
+ * any present tap, gives Hm, bv (and G, xi, info) bit-identical to the entries without the term.  Workspace and the fused /
+ * three-launch forms (rnnpose_lm_fused_tail) as for rnnpose_lm_step_io_f32; the workspace may be shared with it.
+ * Returns 1 for a null obs_depth / theta / K_obs, S < 1, a null src_index with S != B, and a negative or non-finite depth_weight,
+ * depth_gate or edge_tol.                                                                          */
+int rnnpose_lm_normal_eq_rgbd_f64(const float* target, int target_mode, const float* weight, const float* depth,
+                                  float depth_eps, const float* K, const float* G, int B, int H, int W,
+                                  const float* obs_depth, const int* src_index, const float* theta, const float* K_obs,
+                                  int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
+                                  void* workspace, size_t workspace_bytes, double* Hm, double* bv, double* dstats,
+                                  rnnpose_stream_t stream);
+int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const float* weight, const float* depth,
+                                float depth_eps, const float* K, const float* G_in, float* G_out, int B, int H, int W,
+                                int num_iters, double ep_lambda, double lm_lambda, double max_update,
+                                const float* obs_depth, const int* src_index, const float* theta, const float* K_obs,
+                                int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
+                                void* workspace, size_t workspace_bytes, double* Hm, double* bv, float* xi, int* info,
+                                double* dstats, rnnpose_stream_t stream);
 /* The fused steps run ONE launch per Gauss-Newton iteration: the workgroup that arrives last for an image (device-scope ticket
  * in the workspace, which must therefore be ZERO-FILLED when it is allocated) sums the partial records, solves and updates the
  * pose.  rnnpose_lm_fused_tail(0) restores the three-launch form (normal equations, finalize, solve) for measurements. */

@@ -7,6 +7,10 @@
 // upper-triangle + 6 right-hand-side sums in fp64 over a strided set of pixels, a wave64 shuffle tree and
 // one LDS hop reduce the workgroup, and per-workgroup partials are summed in FIXED order by the solve
 // kernel (deterministic: no atomics).  HBM traffic = target + weight + depth read once (16 B/pixel).
+//   lm_rgbd_eq      the same sums with an opt-in 3-D residual from the OBSERVED depth of an RGB-D camera (no counterpart in the reference;
+//                  include/rnnpose_hip.h): + four gathered taps per pixel
+#include <cmath>
+
 #include "geometry.cuh"
 
 namespace {
@@ -15,6 +19,7 @@ using rp::Intr;
 using rp::Pose;
 
 constexpr int NACC = 27;        // 21 (upper triangle of H, row-major) + 6 (b)
+constexpr int NACC_RGBD = 29;   // + the depth term's statistics: [27] active pixels, [28] sum v w omega |r3|^2
 constexpr int PSTRIDE = 32;     // doubles per partial record
 constexpr int LM_THREADS = 256;
 // r04 sweep (B = 4 / B = 8 x 480 x 640, us per fused LM step): 1024 px per workgroup, 4 in flight 40.6 / 70.7; 2048, 4 (r03) 35.9 / 52.4;
@@ -60,13 +65,16 @@ struct LmTail {
   float* xi;
   int* info;
   double ep, lm, max_update;
+  double* dstats;               // (B,2) depth-term statistics of lm_rgbd_eq_kernel, or null (always null for lm_normal_eq_kernel)
 };
-__device__ void lm_finalize_block_one(const double* __restrict__ partials, int nblk, int b, double* __restrict__ Hm, double* __restrict__ bv);
+__device__ void lm_finalize_block_one(const double* __restrict__ partials, int nblk, int b, double* __restrict__ Hm, double* __restrict__ bv,
+                                      double* __restrict__ dstats);
 __device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv, const float* G, int b, double ep, double lm, double max_update,
                              float* G_new, float* xi_out, int* info);
 
-// one pixel's contribution to the 21 + 6 sums (fp64), J and the residual from the TRANSFORMED point
-__device__ __forceinline__ void lm_accumulate(double (&acc)[NACC], float wgt, float dep, float tx, float ty, int x, int y, int target_mode,
+// one pixel's contribution to the 21 + 6 sums (fp64), J and the residual from the TRANSFORMED point (NA >= NACC: the first 27 sums)
+template <int NA>
+__device__ __forceinline__ void lm_accumulate(double (&acc)[NA], float wgt, float dep, float tx, float ty, int x, int y, int target_mode,
                                           float eps, const Intr& k, const Pose& g) {
   const float Z = dep + eps;
   if (target_mode != 0) {
@@ -105,9 +113,11 @@ __device__ __forceinline__ void lm_accumulate(double (&acc)[NACC], float wgt, fl
 }
 
 // the workgroup's 27 sums -> its partial record; FUSED: the last workgroup of the image finalizes, solves and updates the pose
-template <bool FUSED>
-__device__ __forceinline__ void lm_reduce_tail(double (&acc)[NACC], double* __restrict__ partials, const LmTail& tail, int b, int nblk, int bx) {
-  __shared__ double red[LM_THREADS / 64][NACC];
+// NA = NACC, or NACC_RGBD for lm_rgbd_eq_kernel: its two statistics ride in slots 27 and 28 of the same 32-slot butterfly and record
+template <bool FUSED, int NA = NACC>
+__device__ __forceinline__ void lm_reduce_tail(double (&acc)[NA], double* __restrict__ partials, const LmTail& tail, int b, int nblk, int bx) {
+  static_assert(NA <= PSTRIDE, "the partial record has 32 slots");
+  __shared__ double red[LM_THREADS / 64][NA];
   __shared__ int is_last;
   // wave reduction as a butterfly REDUCE-SCATTER (r04): at offset o = 32, 16, 8, 4, 2 a lane keeps the half of its (32, 16, 8, 4,
   // 2) slots that bit o of its lane number selects, sends the other half to lane ^ o and adds what it receives -- 16 + 8 + 4 + 2 +
@@ -118,7 +128,7 @@ __device__ __forceinline__ void lm_reduce_tail(double (&acc)[NACC], double* __re
   {
     double v[32];
 #pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = i < NACC ? acc[i] : 0.0;
+    for (int i = 0; i < 32; ++i) v[i] = i < NA ? acc[i] : 0.0;
 #pragma unroll
     for (int o = 32, n = 32; o >= 2; o >>= 1, n >>= 1) {         // n slots live before the step, n / 2 after
       const bool hi = (lane & o) != 0;
@@ -132,10 +142,10 @@ __device__ __forceinline__ void lm_reduce_tail(double (&acc)[NACC], double* __re
     const double tot = v[0] + rp::shfl_xor_f64(v[0], 1);
     // slot held by this lane pair: bit 5 of the lane chose the upper half of 32, bit 4 of 16, ... bit 1 of 2
     const int slot = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-    if (!(lane & 1) && slot < NACC) red[wave][slot] = tot;
+    if (!(lane & 1) && slot < NA) red[wave][slot] = tot;
   }
   __syncthreads();
-  if (threadIdx.x < NACC) {
+  if (threadIdx.x < NA) {
     double v = red[0][threadIdx.x];
 #pragma unroll
     for (int wv = 1; wv < LM_THREADS / 64; ++wv) v += red[wv][threadIdx.x];
@@ -159,7 +169,7 @@ __device__ __forceinline__ void lm_reduce_tail(double (&acc)[NACC], double* __re
     }
     __syncthreads();
     if (!is_last) return;
-    lm_finalize_block_one(partials, nblk, b, tail.Hm, tail.bv);   // (ends with the values in global memory, written by this block)
+    lm_finalize_block_one(partials, nblk, b, tail.Hm, tail.bv, tail.dstats);   // (ends with the values in global memory, written by this block)
     __syncthreads();
     if (threadIdx.x == 0) lm_solve_one(tail.Hm, tail.bv, tail.G_in, b, tail.ep, tail.lm, tail.max_update, tail.G_out, tail.xi, tail.info);
   }
@@ -222,19 +232,221 @@ __global__ __launch_bounds__(LM_THREADS) void lm_normal_eq_kernel(const float* _
   lm_reduce_tail<FUSED>(acc, partials, tail, b, nblk, static_cast<int>(blockIdx.x));
 }
 
+// ---- the depth-aware step (RGB-D): an opt-in 3-D residual from the OBSERVED depth in the same 27 sums -------------------------------
+// For a crop pixel with matched position t (crop pixel-index coordinates): where t falls in the full observed frame (the affine map
+// that made the image crop, zoom_crop.hip's zoom_crop_pixel continued to non-integer positions), the observed depth zo there
+// (hole-aware: bilinear over four present taps that lie within edge_tol of each other, else the nearest tap, else no term), the
+// observed point Y = zo K_obs^-1 (ix, iy, 1) and, where v holds and |Y.z - X1.z| <= depth_gate, the residual r3 = Y - X1 with
+// J_T = [I | -[X1]x] and the scale omega = depth_weight fx fy / Zc^2 (0 where the `tiny` clamp applies): a lateral 3-D error in the
+// pixel^2 units of the 2-D term.  Per-pixel quantities are fp32 in the order written here, the sums fp64.
+struct LmDepthTerm {
+  const float* obs;             // (S,Ho,Wo) observed depth, 0 / negative / non-finite = no measurement
+  const int* src_index;         // (B) frame of every object, or null: object b reads frame b
+  const float* theta;           // (B,2,3) the views' crop maps
+  const float* K_obs;           // (B,3,3) full-frame intrinsics
+  int S, Ho, Wo;
+  float weight, gate, edge_tol;
+};
+
+struct LmFrame {                // the per-image constants of the depth term, loaded once per workgroup
+  const float* obs;             // frame of this object (frame 0 with ok == false)
+  bool ok;                      // the frame index is inside [0, S)
+  float th[6];
+  Intr ko;
+  int Ho, Wo;
+};
+
+// position of the target of crop pixel (x, y) in the observed frame, pixel-index coordinates (fp32, zoom_crop_pixel's operation order)
+__device__ __forceinline__ void lm_obs_position(float tx, float ty, int x, int y, int target_mode, int H, int W, const LmFrame& f, float& ix,
+                                                float& iy) {
+  if (target_mode != 0) {                                            // (lm_accumulate's own fp32 sum)
+    tx += static_cast<float>(x);
+    ty += static_cast<float>(y);
+  }
+  const float bx = (2.f * tx + 1.f) / W - 1.f, by = (2.f * ty + 1.f) / H - 1.f;
+  const float gx = f.th[0] * bx + f.th[1] * by + f.th[2];
+  const float gy = f.th[3] * bx + f.th[4] * by + f.th[5];
+  ix = ((gx + 1.f) * f.Wo - 1.f) * 0.5f;
+  iy = ((gy + 1.f) * f.Ho - 1.f) * 0.5f;
+}
+
+// north-west tap of (ix, iy); a non-finite or huge position gets a tap far outside every frame
+__device__ __forceinline__ void lm_obs_corner(float ix, float iy, int& x0, int& y0) {
+  const bool sane = fabsf(ix) < 1.0e8f && fabsf(iy) < 1.0e8f;      // (false for NaN and infinity)
+  x0 = sane ? static_cast<int>(floorf(ix)) : -10;
+  y0 = sane ? static_cast<int>(floorf(iy)) : -10;
+}
+
+__device__ __forceinline__ bool lm_tap_present(bool inside, float z) { return inside && z > 0.f && __builtin_isfinite(z); }
+
+// the observed point at (ix, iy) from the four taps (nw, ne, sw, se; loaded at CLAMPED positions: `inside` decides) -> has a depth?
+__device__ __forceinline__ bool lm_obs_point(float ix, float iy, const float (&z)[4], const LmFrame& f, float edge_tol, float& Yx, float& Yy,
+                                             float& Yz) {
+  int x0, y0;
+  lm_obs_corner(ix, iy, x0, y0);
+  const bool vx0 = x0 >= 0 && x0 < f.Wo, vx1 = x0 + 1 >= 0 && x0 + 1 < f.Wo;
+  const bool vy0 = y0 >= 0 && y0 < f.Ho, vy1 = y0 + 1 >= 0 && y0 + 1 < f.Ho;
+  const bool p00 = lm_tap_present(f.ok && vy0 && vx0, z[0]), p10 = lm_tap_present(f.ok && vy0 && vx1, z[1]);
+  const bool p01 = lm_tap_present(f.ok && vy1 && vx0, z[2]), p11 = lm_tap_present(f.ok && vy1 && vx1, z[3]);
+  const float fx0 = floorf(ix), fy0 = floorf(iy);
+  const float fx1 = fx0 + 1.f, fy1 = fy0 + 1.f;
+  float zo;
+  bool has;
+  const float zmax = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])), zmin = fminf(fminf(z[0], z[1]), fminf(z[2], z[3]));
+  if (p00 && p10 && p01 && p11 && zmax - zmin <= edge_tol) {
+    // weights and order of zoom_crop_pixel (torch's grid_sampler: nw, ne, sw, se)
+    const float w00 = (fx1 - ix) * (fy1 - iy), w10 = (ix - fx0) * (fy1 - iy), w01 = (fx1 - ix) * (iy - fy0), w11 = (ix - fx0) * (iy - fy0);
+    zo = 0.f;
+    zo += z[0] * w00;
+    zo += z[1] * w10;
+    zo += z[2] * w01;
+    zo += z[3] * w11;
+    has = true;
+  } else {                                                           // a hole or a depth edge under the footprint: the nearest tap, if present
+    const bool east = floorf(ix + 0.5f) != fx0, south = floorf(iy + 0.5f) != fy0;
+    zo = south ? (east ? z[3] : z[2]) : (east ? z[1] : z[0]);
+    has = south ? (east ? p11 : p01) : (east ? p10 : p00);
+  }
+  Yx = zo * (ix - f.ko.cx) / f.ko.fx;                                // Y = zo K_obs^-1 (ix, iy, 1), the back-projection of geometry.cuh
+  Yy = zo * (iy - f.ko.cy) / f.ko.fy;
+  Yz = zo;
+  return has;
+}
+
+// one ACTIVE pixel's depth term in the 21 + 6 sums and the cost statistic: H += s J_T^T J_T, b += s J_T^T r3 with J_T = [I | A],
+// A = -[X1]x:  J_T^T J_T = [I A; A^T A^T A],  A^T A = |X1|^2 I - X1 X1^T,  J_T^T r3 = (r3, X1 x r3)
+__device__ __forceinline__ void lm_accumulate_depth(double (&acc)[NACC_RGBD], double s, float X1f, float Y1f, float Z1f, float Yx, float Yy,
+                                                    float Yz) {
+  const double X = X1f, Y = Y1f, Z = Z1f;
+  const double rx = static_cast<double>(Yx) - X, ry = static_cast<double>(Yy) - Y, rz = static_cast<double>(Yz) - Z;
+  // upper triangle, row-major: row 0 at 0, row 1 at 6, row 2 at 11, row 3 at 15, row 4 at 18, row 5 at 20
+  acc[0] += s;            acc[4] += s * Z;         acc[5] += s * (-Y);
+  acc[6] += s;            acc[8] += s * (-Z);      acc[10] += s * X;
+  acc[11] += s;           acc[12] += s * Y;        acc[13] += s * (-X);
+  acc[15] += s * (Y * Y + Z * Z);  acc[16] += s * (-(X * Y));        acc[17] += s * (-(X * Z));
+  acc[18] += s * (X * X + Z * Z);  acc[19] += s * (-(Y * Z));
+  acc[20] += s * (X * X + Y * Y);
+  acc[21] += s * rx;
+  acc[22] += s * ry;
+  acc[23] += s * rz;
+  acc[24] += s * (Y * rz - Z * ry);
+  acc[25] += s * (Z * rx - X * rz);
+  acc[26] += s * (X * ry - Y * rx);
+  acc[28] += s * (rx * rx + ry * ry + rz * rz);
+}
+
+// lm_normal_eq_kernel with the depth term: the same trips, the same order of the 2-D sums (lm_accumulate itself), the same tail.  The
+// four depth taps of a trip's LM_BATCH pixels are a SECOND batch of loads, issued together once the targets have arrived.
+template <bool FUSED>
+__global__ __launch_bounds__(LM_THREADS) void lm_rgbd_eq_kernel(const float* __restrict__ target, int target_mode,
+                                                                const float* __restrict__ weight, const float* __restrict__ depth,
+                                                                float eps, const float* __restrict__ K, const float* __restrict__ G,
+                                                                int H, int W, const LmDepthTerm dt, double* __restrict__ partials,
+                                                                const LmTail tail) {
+  const int b = blockIdx.y;
+  const int nblk = gridDim.x;
+  const long long P = static_cast<long long>(H) * W;
+  const Intr k = rp::load_intr(K, b);
+  const Pose g = rp::load_pose(G, b);
+  LmFrame f;
+  {
+    const int s = dt.src_index ? dt.src_index[b] : b;
+    f.ok = s >= 0 && s < dt.S;                                       // (the caller has refused it on the host; the second fence)
+    f.obs = dt.obs + static_cast<long long>(f.ok ? s : 0) * dt.Ho * dt.Wo;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) f.th[i] = dt.theta[b * 6 + i];
+    f.ko = rp::load_intr(dt.K_obs, b);
+    f.Ho = dt.Ho;
+    f.Wo = dt.Wo;
+  }
+  double acc[NACC_RGBD];
+#pragma unroll
+  for (int i = 0; i < NACC_RGBD; ++i) acc[i] = 0.0;
+
+  const long long stride = static_cast<long long>(nblk) * LM_THREADS;
+  for (long long t0 = static_cast<long long>(blockIdx.x) * LM_THREADS + threadIdx.x; t0 < P; t0 += LM_BATCH * stride) {
+    float wgt_[LM_BATCH], dep_[LM_BATCH], tx_[LM_BATCH], ty_[LM_BATCH];
+#pragma unroll
+    for (int j = 0; j < LM_BATCH; ++j) {
+      const long long tj = t0 + j * stride;
+      const long long t = tj < P ? tj : P - 1;
+      wgt_[j] = weight[b * P + t];
+      dep_[j] = depth[b * P + t];
+      if (target_mode == 0) {
+        const float2 tt = *reinterpret_cast<const float2*>(target + (b * P + t) * 2);
+        tx_[j] = tt.x;
+        ty_[j] = tt.y;
+      } else {
+        tx_[j] = target[(static_cast<long long>(b) * 2 + 0) * P + t];
+        ty_[j] = target[(static_cast<long long>(b) * 2 + 1) * P + t];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // second batch: the taps, unconditionally and at positions clamped into the frame (lm_obs_point decides which of them count).  Only the
+    // taps stay live across the loads: (ix, iy) are formed again behind them -- keeping 16 more registers took the kernel to 1 wave per SIMD
+    float z_[LM_BATCH][4];
+#pragma unroll
+    for (int j = 0; j < LM_BATCH; ++j) {
+      const long long tj = t0 + j * stride;
+      const unsigned tu = static_cast<unsigned>(tj < P ? tj : P - 1);
+      const int y = static_cast<int>(tu / static_cast<unsigned>(W)), x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
+      float ix, iy;
+      lm_obs_position(tx_[j], ty_[j], x, y, target_mode, H, W, f, ix, iy);
+      int x0, y0;
+      lm_obs_corner(ix, iy, x0, y0);
+      const int xa = min(max(x0, 0), f.Wo - 1), xb = min(max(x0 + 1, 0), f.Wo - 1);
+      const int ya = min(max(y0, 0), f.Ho - 1) * f.Wo, yb = min(max(y0 + 1, 0), f.Ho - 1) * f.Wo;
+      z_[j][0] = f.obs[ya + xa];
+      z_[j][1] = f.obs[ya + xb];
+      z_[j][2] = f.obs[yb + xa];
+      z_[j][3] = f.obs[yb + xb];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < LM_BATCH; ++j) {
+      const long long t = t0 + j * stride;
+      if (t >= P) break;
+      const unsigned tu = static_cast<unsigned>(t);
+      const int y = static_cast<int>(tu / static_cast<unsigned>(W)), x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
+      const float wgt = wgt_[j];
+      // the gate is evaluated for EVERY pixel (fp32, no fp64 chain): the count of active pixels does not depend on the weights
+      const rp::Reproj r = rp::reproject(dep_[j] + eps, static_cast<float>(x), static_cast<float>(y), k, g);
+      const bool valid = (r.Z0 > rp::kMinDepthValid) && (r.Z1 > rp::kMinDepthValid);
+      float Yx, Yy, Yz, ix, iy;
+      lm_obs_position(tx_[j], ty_[j], x, y, target_mode, H, W, f, ix, iy);
+      const bool has = lm_obs_point(ix, iy, z_[j], f, dt.edge_tol, Yx, Yy, Yz);
+      const bool active = has && valid && fabsf(Yz - r.Z1) <= dt.gate;
+      acc[27] += active ? 1.0 : 0.0;
+      // the zero-weight-wave skip of lm_normal_eq_kernel, unchanged (a zero weight zeroes the depth term's sums as well)
+      const bool skippable = wgt == 0.f && __builtin_isfinite(tx_[j]) && __builtin_isfinite(ty_[j]) && __builtin_isfinite(dep_[j]);
+      if (__builtin_amdgcn_ballot_w64(!skippable) == 0ull) continue;
+      lm_accumulate(acc, wgt, dep_[j], tx_[j], ty_[j], x, y, target_mode, eps, k, g);
+      const bool tiny = r.Zc <= rp::kMinDepthProj + 0.01f;
+      const float zi2 = tiny ? 0.f : 1.0f / (r.Zc * r.Zc);
+      const float omega = dt.weight * (k.fx * k.fy) * zi2;
+      const double s = (valid ? static_cast<double>(wgt) : 0.0) * static_cast<double>(omega);
+      // a pixel without a measurement, outside the gate or with a zero scale adds NOTHING: with depth_weight = 0 or an empty observed
+      // depth the 27 sums are lm_normal_eq_kernel's bit for bit
+      if (active && s != 0.0) lm_accumulate_depth(acc, s, r.X1, r.Y1, r.Z1, Yx, Yy, Yz);
+    }
+  }
+  lm_reduce_tail<FUSED, NACC_RGBD>(acc, partials, tail, b, nblk, static_cast<int>(blockIdx.x));
+}
+
 // sums the block partials in fixed order and expands to full H (6x6) and b (6)
+// dstats != null (lm_rgbd_eq_kernel's records only: the plain kernel never writes slots 27, 28): the two depth-term statistics too
 __device__ void lm_finalize_block_one(const double* __restrict__ partials, int nblk, int b, double* __restrict__ Hm,
-                                      double* __restrict__ bv) {
+                                      double* __restrict__ bv, double* __restrict__ dstats) {
   // 8 groups of 32 lanes walk the partial records with stride 8 (each load is one coalesced 256-byte record), then
   // the 8 group sums are added in fixed order: deterministic, and 8x shorter than one serial chain per value.
   __shared__ double grp[8][PSTRIDE];
-  __shared__ double s[NACC];
+  __shared__ double s[NACC_RGBD];
   const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
   double v = 0.0;
   for (int i = g; i < nblk; i += 8) v += partials[(static_cast<long long>(b) * nblk + i) * PSTRIDE + k];
   grp[g][k] = v;
   __syncthreads();
-  if (threadIdx.x < NACC) {
+  if (threadIdx.x < (dstats ? NACC_RGBD : NACC)) {
     double t = 0.0;
     for (int q = 0; q < 8; ++q) t += grp[q][threadIdx.x];
     s[threadIdx.x] = t;
@@ -247,12 +459,14 @@ __device__ void lm_finalize_block_one(const double* __restrict__ partials, int n
     Hm[b * 36 + threadIdx.x] = s[idx];
   } else if (threadIdx.x < 42) {
     bv[b * 6 + (threadIdx.x - 36)] = s[21 + (threadIdx.x - 36)];
+  } else if (dstats && threadIdx.x < 44) {
+    dstats[b * 2 + (threadIdx.x - 42)] = s[NACC + (threadIdx.x - 42)];
   }
 }
 
 __global__ __launch_bounds__(256) void lm_finalize_kernel(const double* __restrict__ partials, int nblk,
-                                                          double* __restrict__ Hm, double* __restrict__ bv) {
-  lm_finalize_block_one(partials, nblk, blockIdx.x, Hm, bv);
+                                                          double* __restrict__ Hm, double* __restrict__ bv, double* __restrict__ dstats) {
+  lm_finalize_block_one(partials, nblk, blockIdx.x, Hm, bv, dstats);
 }
 
 // ---- SE(3) exponential, fp32, same branch structure as geometry/se3.py:228-281 ----
@@ -478,8 +692,30 @@ int launch_normal_eq(const float* target, int target_mode, const float* weight, 
                      const float* K, const float* G, int B, int H, int W, void* workspace, double* Hm, double* bv,
                      hipStream_t st) {
   const int nblk = launch_normal_eq_partials(target, target_mode, weight, depth, eps, K, G, B, H, W, workspace, st);
-  hipLaunchKernelGGL(lm_finalize_kernel, dim3(B), dim3(256), 0, st, lm_partials(workspace, B), nblk, Hm, bv);
+  hipLaunchKernelGGL(lm_finalize_kernel, dim3(B), dim3(256), 0, st, lm_partials(workspace, B), nblk, Hm, bv, static_cast<double*>(nullptr));
   return 0;
+}
+
+// the depth-aware step: partial sums (+ fused tail), or partial sums, finalize (with the statistics) and solve as three launches
+void launch_lm_rgbd(bool fused, const float* target, int target_mode, const float* weight, const float* depth, float eps, const float* K,
+                    const float* G_in, float* G_out, int B, int H, int W, const LmDepthTerm& dt, double ep, double lm, double max_update,
+                    void* workspace, double* Hm, double* bv, float* xi, int* info, double* dstats, hipStream_t st) {
+  const long long P = static_cast<long long>(H) * W;
+  const int nblk = lm_blocks_per_image(P);
+  if (fused) {
+    LmTail tail{};
+    tail.tickets = static_cast<int*>(workspace);
+    tail.Hm = Hm; tail.bv = bv; tail.G_in = G_in; tail.G_out = G_out; tail.xi = xi; tail.info = info;
+    tail.ep = ep; tail.lm = lm; tail.max_update = max_update; tail.dstats = dstats;
+    hipLaunchKernelGGL(lm_rgbd_eq_kernel<true>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps, K, G_in,
+                       H, W, dt, lm_partials(workspace, B), tail);
+    return;
+  }
+  hipLaunchKernelGGL(lm_rgbd_eq_kernel<false>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps, K, G_in,
+                     H, W, dt, lm_partials(workspace, B), LmTail{});
+  hipLaunchKernelGGL(lm_finalize_kernel, dim3(B), dim3(256), 0, st, lm_partials(workspace, B), nblk, Hm, bv, dstats);
+  if (G_out)
+    hipLaunchKernelGGL(lm_solve_update_kernel, dim3(rp::cdiv(B, 64)), dim3(64), 0, st, Hm, bv, G_in, B, ep, lm, max_update, G_out, xi, info);
 }
 
 }  // namespace
@@ -563,6 +799,56 @@ int rnnpose_lm_step_io_f32(const float* target, int target_mode, const float* we
   RP_REQUIRE(num_iters >= 1, "rnnpose_lm_step_io_f32", "needs at least one iteration (G_out would stay unwritten)");
   return lm_step_impl("rnnpose_lm_step_io_f32", target, target_mode, weight, depth, depth_eps, K, G_in, G_out, B, H, W,
                       num_iters, ep_lambda, lm_lambda, max_update, workspace, workspace_bytes, Hm, bv, xi, info, stream);
+}
+
+// the depth arguments shared by the two RGB-D entries
+static int lm_rgbd_check(const char* fn, const float* obs_depth, const int* src_index, const float* theta, const float* K_obs, int B, int S,
+                         int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol) {
+  RP_REQUIRE(obs_depth && theta && K_obs, fn, "null obs_depth / theta / K_obs");
+  RP_REQUIRE(S >= 1 && Ho > 0 && Wo > 0 && static_cast<long long>(Ho) * Wo < (1LL << 31), fn, "bad observed-frame size (S >= 1, Ho, Wo > 0)");
+  RP_REQUIRE(src_index || S == B, fn, "src_index is null: the observed depth must hold one frame per object (S == B)");
+  RP_REQUIRE(std::isfinite(depth_weight) && depth_weight >= 0.f, fn, "depth_weight must be finite and >= 0");
+  RP_REQUIRE(std::isfinite(depth_gate) && depth_gate >= 0.f, fn, "depth_gate must be finite and >= 0");
+  RP_REQUIRE(std::isfinite(edge_tol) && edge_tol >= 0.f, fn, "edge_tol must be finite and >= 0");
+  return 0;
+}
+
+int rnnpose_lm_normal_eq_rgbd_f64(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
+                                  const float* K, const float* G, int B, int H, int W, const float* obs_depth, const int* src_index,
+                                  const float* theta, const float* K_obs, int S, int Ho, int Wo, float depth_weight, float depth_gate,
+                                  float edge_tol, void* workspace, size_t workspace_bytes, double* Hm, double* bv, double* dstats,
+                                  rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_lm_normal_eq_rgbd_f64";
+  RP_REQUIRE(target && weight && depth && K && G && workspace && Hm && bv, fn, "null pointer");
+  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
+  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31), fn, "bad size");
+  if (lm_rgbd_check(fn, obs_depth, src_index, theta, K_obs, B, S, Ho, Wo, depth_weight, depth_gate, edge_tol)) return 1;
+  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
+  const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
+  launch_lm_rgbd(false, target, target_mode, weight, depth, depth_eps, K, G, nullptr, B, H, W, dt, 0.0, 0.0, 0.0, workspace, Hm, bv, nullptr,
+                 nullptr, dstats, rp::as_stream(stream));
+  return rp::check_launch(fn);
+}
+
+int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
+                                const float* K, const float* G_in, float* G_out, int B, int H, int W, int num_iters, double ep_lambda,
+                                double lm_lambda, double max_update, const float* obs_depth, const int* src_index, const float* theta,
+                                const float* K_obs, int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
+                                void* workspace, size_t workspace_bytes, double* Hm, double* bv, float* xi, int* info, double* dstats,
+                                rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_lm_step_rgbd_io_f32";
+  RP_REQUIRE(target && weight && depth && K && G_in && G_out && workspace && Hm && bv && xi, fn, "null pointer");
+  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
+  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31), fn, "bad size");
+  RP_REQUIRE(num_iters >= 1, fn, "needs at least one iteration (G_out would stay unwritten)");
+  if (lm_rgbd_check(fn, obs_depth, src_index, theta, K_obs, B, S, Ho, Wo, depth_weight, depth_gate, edge_tol)) return 1;
+  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
+  const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
+  hipStream_t st = rp::as_stream(stream);
+  for (int it = 0; it < num_iters; ++it)                 // later iterations continue in place on the output, as rnnpose_lm_step_io_f32 does
+    launch_lm_rgbd(g_lm_fused && info, target, target_mode, weight, depth, depth_eps, K, it == 0 ? G_in : G_out, G_out, B, H, W, dt, ep_lambda,
+                   lm_lambda, max_update, workspace, Hm, bv, xi, info, dstats, st);
+  return rp::check_launch(fn);
 }
 
 int rnnpose_se3_exp_f32(const float* xi, int B, float* out, rnnpose_stream_t stream) {

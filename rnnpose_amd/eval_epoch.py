@@ -175,8 +175,11 @@ class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
     def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None, occlusion=None,
-                 occlusion_margin=0.0):
-        """occlusion="frame" (PoseRefiner's argument; occlusion_margin in the models' length unit): refine_frame masks the pixels of
+                 occlusion_margin=0.0, depth_term=None):
+        """depth_term (PoseRefiner's argument: True or a dict of depth_weight / depth_gate / edge_tol): `refine` and `refine_frame`
+        hand the frames' observed depth (EvalItem.depth) to the refiner, whose LM steps then carry its 3-D residual; an item without
+        depth raises ValueError.  The statistics of the last call are in `last_depth_stats`.
+        occlusion="frame" (PoseRefiner's argument; occlusion_margin in the models' length unit): refine_frame masks the pixels of
         every object that another object of the same frame hides under the current pose estimates.  `refine` -- one class per
         batch, one image per object -- has no pairs and is unaffected.  With a ready-made `refiner`, set it there."""
         from .evaluator import LineMODEvaluator
@@ -192,8 +195,12 @@ class HipEpoch:
         self.cfg = cfg if cfg is not None else default_config()
         if refiner is not None and occlusion is not None:
             raise ValueError("HipEpoch(refiner=..., occlusion=...): construct the refiner with occlusion= instead")
+        if refiner is not None and depth_term is not None:
+            raise ValueError("HipEpoch(refiner=..., depth_term=...): construct the refiner with depth_term= instead")
         self.refiner = refiner if refiner is not None else \
-            PoseRefiner(self.cfg, renderer=self.renderer, occlusion=occlusion, occlusion_margin=occlusion_margin).to(self.device).eval()
+            PoseRefiner(self.cfg, renderer=self.renderer, occlusion=occlusion, occlusion_margin=occlusion_margin,
+                        depth_term=depth_term).to(self.device).eval()
+        self.last_depth_stats = None
         self.symmetric = tuple(symmetric)
         # desc2d: a descriptor2d.SuperPoint2D -- items without geofea_2d get theirs from the batch image on the device, as
         # model/RNNPose.py:162 computes them (HybridNet.py:97 keeps the descriptors only)
@@ -226,8 +233,17 @@ class HipEpoch:
         T0 = torch.as_tensor(np.stack([it.pose_init for it in batch]).astype(np.float32)).to(dev)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=m.fea_3d.to(dev), Tj_gt=SE3Sequence(matrix=Tg[:, None]),
-                           obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2)
+                           obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2, **self._observed_depth(batch))
+        self.last_depth_stats = out.get("depth_stats")
         return out["Ti_pred"].G.reshape(-1, 4, 4)
+
+    def _observed_depth(self, frames):
+        """-> the refiner's depth= argument for these frames' items ({} when the depth term is off)."""
+        if getattr(self.refiner, "depth_term", None) is None:
+            return {}
+        if any(it.depth is None for it in frames):
+            raise ValueError("depth_term: every item needs the observed depth of its frame (EvalItem.depth)")
+        return dict(depth=torch.stack([it.depth for it in frames]).to(self.device).float())
 
     def _resident_tables(self):
         """On the first refine_frame: lay every class's [context | descriptor] table out once in the refiner's renderer
@@ -268,7 +284,8 @@ class HipEpoch:
             fea = [self.models[n].fea_3d.to(dev)[0] for n in names]
             geo = [self.models[n].geofea_3d.to(dev)[0] for n in names]
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=fea, Tj_gt=SE3Sequence(matrix=Tg[:, None]),
-                           obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index)
+                           obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index, **self._observed_depth(firsts))
+        self.last_depth_stats = out.get("depth_stats")
         return out["Ti_pred"].G.reshape(-1, 4, 4)
 
     def bop_metrics(self, batch, pose_pred, want_errors=False):

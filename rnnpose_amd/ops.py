@@ -472,6 +472,112 @@ def lm_step(target, weight, depth, K, G, num_iters=1, ep_lambda=100.0, lm_lambda
     return G, Hm, bv, xi, info
 
 
+DEPTH_TERM_DEFAULTS = dict(depth_weight=1.0, depth_gate=0.05, edge_tol=0.02)      # DESIGN.md section 18 (gate and edge tolerance: unmeasured choices)
+
+
+def depth_term_params(depth_term):
+    """None / False -> None (term off); True -> the defaults; a dict of any of depth_weight, depth_gate, edge_tol -> the full dict.
+    Values must be finite and >= 0 (ValueError)."""
+    if depth_term is None or depth_term is False:
+        return None
+    p = dict(DEPTH_TERM_DEFAULTS)
+    if depth_term is not True:
+        extra = set(depth_term) - set(p)
+        if extra:
+            raise ValueError(f"depth_term: unknown keys {sorted(extra)}; known: {sorted(p)}")
+        p.update({k: float(v) for k, v in depth_term.items()})
+    for k, v in p.items():
+        if not (v >= 0.0 and v != float("inf")):
+            raise ValueError(f"depth_term: {k} must be finite and >= 0, got {v}")
+    return p
+
+
+def _rgbd_args(fn, B, obs_depth, theta, K_obs, src_index, index_rows, depth_weight, depth_gate, edge_tol):
+    """Host-side checks of the depth arguments -> (obs_depth, theta, K_obs, index device tensor or None, S, Ho, Wo)."""
+    obs_depth, theta, K_obs = _chk(obs_depth, "obs_depth"), _chk(theta, "theta"), _chk(K_obs, "K_obs")
+    if obs_depth.dim() == 4 and obs_depth.shape[1] == 1:
+        obs_depth = obs_depth[:, 0]
+    if obs_depth.dim() != 3 or obs_depth.numel() == 0:
+        raise ValueError(f"{fn}: obs_depth must be (S,Ho,Wo) or (S,1,Ho,Wo), got {tuple(obs_depth.shape)}")
+    S, Ho, Wo = obs_depth.shape
+    if tuple(theta.shape) != (B, 2, 3):
+        raise ValueError(f"{fn}: theta must be ({B},2,3), got {tuple(theta.shape)}")
+    if tuple(K_obs.shape) != (B, 3, 3):
+        raise ValueError(f"{fn}: K_obs must be ({B},3,3), got {tuple(K_obs.shape)}")
+    for name, v in (("depth_weight", depth_weight), ("depth_gate", depth_gate), ("edge_tol", edge_tol)):
+        if not (float(v) >= 0.0 and float(v) != float("inf")):
+            raise ValueError(f"{fn}: {name} must be finite and >= 0, got {v}")
+    idx = None
+    if src_index is None:
+        if S != B:
+            raise ValueError(f"{fn}: without src_index the observed depth holds one frame per object: {S} frames, {B} objects")
+    else:
+        if not isinstance(src_index, SourceIndex):
+            src_index = SourceIndex(src_index, S, obs_depth.device)
+        b0, b1 = index_rows if index_rows is not None else (0, len(src_index))
+        if src_index.S != S or not 0 <= b0 < b1 <= len(src_index) or b1 - b0 != B:
+            raise ValueError(f"{fn}: src_index rows [{b0}, {b1}) of {len(src_index)} objects in {src_index.S} frames; there are {B} objects, "
+                             f"{S} frames")
+        idx = src_index.dev[b0:b1]
+    return obs_depth.contiguous(), theta, K_obs, idx, S, Ho, Wo
+
+
+def lm_normal_eq_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_index=None, depth_weight=1.0, depth_gate=0.05,
+                      edge_tol=0.02, eps: float = 1e-5, index_rows=None):
+    """lm_normal_eq with the depth term of the observed depth (include/rnnpose_hip.h).
+    obs_depth (S,Ho,Wo) or (S,1,Ho,Wo); theta (B,2,3) the crop maps; K_obs (B,3,3) full-frame intrinsics; src_index: an
+    ops.SourceIndex, B integers or None (S == B); index_rows (b0, b1): the objects are rows [b0, b1) of src_index.
+    -> Hm (B,6,6), bv (B,6), dstats (B,2) fp64 [active pixels, sum v w omega |r3|^2]."""
+    target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
+    K, G = _chk(K, "intrinsics"), _chk(G, "G")
+    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
+    mode = _target_mode(target, H, W)
+    obs_depth, theta, K_obs, idx, S, Ho, Wo = _rgbd_args("lm_normal_eq_rgbd", B, obs_depth, theta, K_obs, src_index, index_rows, depth_weight,
+                                                         depth_gate, edge_tol)
+    ws, n = _workspace(B, H, W, depth.device)
+    Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
+    bv = torch.empty(B, 6, device=depth.device, dtype=F64)
+    dstats = torch.empty(B, 2, device=depth.device, dtype=F64)
+    _launch("rnnpose_lm_normal_eq_rgbd_f64", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(G), B, H, W, _ptr(obs_depth),
+            _ptr(idx), _ptr(theta), _ptr(K_obs), S, Ho, Wo, float(depth_weight), float(depth_gate), float(edge_tol), _ptr(ws), n, _ptr(Hm),
+            _ptr(bv), _ptr(dstats), _stream(), nbytes=32.0 * B * H * W, work=300.0 * B * H * W)
+    return Hm, bv, dstats
+
+
+def lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_index=None, depth_weight=1.0, depth_gate=0.05, edge_tol=0.02,
+                 num_iters=1, ep_lambda=100.0, lm_lambda=1e-4, max_update=1.0, eps=1e-5, out=None, slot=0, index_rows=None):
+    """lm_step with the depth term (arguments: lm_normal_eq_rgbd); num_iters >= 1 fused GN steps.
+    -> (G_new (B,4,4), Hm, bv, xi, info, dstats (B,2) fp64) of the last iteration.  out: optional preallocated
+    (G_new, Hm, bv, xi, info, dstats) views to write into; slot: workspace slot, as for lm_step."""
+    _apply_lm_env()
+    if int(num_iters) < 1:
+        raise ValueError("lm_step_rgbd: num_iters must be >= 1")
+    target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
+    K = _chk(K, "intrinsics")
+    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
+    mode = _target_mode(target, H, W)
+    obs_depth, theta, K_obs, idx, S, Ho, Wo = _rgbd_args("lm_step_rgbd", B, obs_depth, theta, K_obs, src_index, index_rows, depth_weight,
+                                                         depth_gate, edge_tol)
+    ws, n = _workspace(B, H, W, depth.device, slot)
+    Gin = _chk(G, "G").reshape(-1, 4, 4)
+    if not Gin.is_contiguous():
+        Gin = Gin.contiguous()
+    if out is not None:
+        Gd, Hm, bv, xi, info, dstats = out
+    else:
+        Gd = torch.empty(B, 4, 4, device=depth.device, dtype=F32)
+        Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
+        bv = torch.empty(B, 6, device=depth.device, dtype=F64)
+        xi = torch.empty(B, 6, device=depth.device, dtype=F32)
+        info = torch.empty(B, device=depth.device, dtype=torch.int32)
+        dstats = torch.empty(B, 2, device=depth.device, dtype=F64)
+    _launch("rnnpose_lm_step_rgbd_io_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(Gin), _ptr(Gd), B, H, W,
+            int(num_iters), float(ep_lambda), float(lm_lambda), float(max_update), _ptr(obs_depth), _ptr(idx), _ptr(theta), _ptr(K_obs), S, Ho,
+            Wo, float(depth_weight), float(depth_gate), float(edge_tol), _ptr(ws), n, _ptr(Hm), _ptr(bv), _ptr(xi), _ptr(info), _ptr(dstats),
+            _stream(), nbytes=32.0 * B * H * W * int(num_iters), work=300.0 * B * H * W * int(num_iters))
+    return Gd, Hm, bv, xi, info, dstats
+
+
 _lm_fused_env_applied = False
 
 
@@ -1630,6 +1736,13 @@ class SourceIndex:
             raise ValueError(f"src_index entries must lie in [0, {self.S}) and there must be at least one: got {bad[:4] or host}")
         self.host = tuple(host)
         self.dev = torch.tensor(host, dtype=torch.int32, device=device)
+
+    @classmethod
+    def from_device(cls, dev, host, S):
+        """A checked index over another device copy `dev` of the same entries (the persistent input buffers of a captured graph)."""
+        obj = cls.__new__(cls)
+        obj.S, obj.host, obj.dev = int(S), tuple(host), dev
+        return obj
 
     def __len__(self):
         return len(self.host)

@@ -79,8 +79,13 @@ class SynImgTail:
 class PoseRefiner(nn.Module):
     def __init__(self, cfg=None, reuse=False, schedule=None, use_regressor=True, is_calibrated=True,
                  bn_is_training=False, is_training=True, renderer=None, fused=True,
-                 img_fea_enc_weights=None, use_graph=True, literal_legacy_pose=None, occlusion=None, occlusion_margin=None):
-        """occlusion (or cfg["occlusion"]; default None) / occlusion_margin (or cfg["occlusion_margin"]; default 0): "frame" masks, in
+                 img_fea_enc_weights=None, use_graph=True, literal_legacy_pose=None, occlusion=None, occlusion_margin=None,
+                 depth_term=None):
+        """depth_term (or cfg["depth_term"]; default None = off): True, or a dict of any of depth_weight, depth_gate, edge_tol
+        (ops.DEPTH_TERM_DEFAULTS) -- forward(..., depth=) then adds the 3-D residual of the observed depth to every
+        LM step (ops.lm_step_rgbd) and the returned dict carries `depth_stats`.  Off, or without a `depth`, the code path is the plain one,
+        launch for launch.
+        occlusion (or cfg["occlusion"]; default None) / occlusion_margin (or cfg["occlusion_margin"]; default 0): "frame" masks, in
         every outer iteration, the pixels of each object's synthetic depth that another object of the same frame (same image_index
         entry) hides under the CURRENT pose estimates of the whole batch (render_adapter.RendererAdapter); the returned dict then
         carries `occlusion_visible`, the last outer iteration's map.  The pass runs in the eager render hand-off: the loop kernels,
@@ -95,6 +100,7 @@ class PoseRefiner(nn.Module):
         self.literal_legacy_pose = bool(cfg.get("literal_legacy_pose", True) if literal_legacy_pose is None else literal_legacy_pose)
         self.occlusion = cfg.get("occlusion", None) if occlusion is None else occlusion
         self.occlusion_margin = float(cfg.get("occlusion_margin", 0.0) if occlusion_margin is None else occlusion_margin)
+        self.depth_term = ops.depth_term_params(cfg.get("depth_term", None) if depth_term is None else depth_term)
         if self.occlusion not in (None, "frame"):
             raise ValueError(f'occlusion must be None or "frame", got {self.occlusion!r}')
         self.reuse = reuse
@@ -263,15 +269,17 @@ class PoseRefiner(nn.Module):
         info = small[o[4]:o[5]].view(torch.int32).view(B)
         return flow_up, wmap, Gn, Hm, bv, xi, info
 
-    def _loop_buffers(self, B, H, W, h, w, n, dev):
+    def _loop_buffers(self, B, H, W, h, w, n, dev, rgbd=None):
         """Output / scratch buffers of the n inner iterations of one outer iteration: big (n, B*3*H*W) and small (n, .)
-        rows = iteration i (see _out_views); coords (n,B,2,h,w) the re-projected low-res coordinates."""
+        rows = iteration i (see _out_views); coords (n,B,2,h,w) the re-projected low-res coordinates; with the depth term, dstats
+        (n,B,2) fp64 its statistics."""
         big = torch.empty(n, B * 3 * H * W, device=dev, dtype=torch.float32)
         small = torch.empty(n, -(-B * 428 // 16) * 16, device=dev, dtype=torch.uint8)     # rows 16-byte aligned (fp64 views)
+        extra = {} if rgbd is None else dict(dstats=torch.empty(n, B, 2, device=dev, dtype=torch.float64))
         return dict(big=big, small=small, coords=torch.empty(n, B, 2, h, w, device=dev, dtype=torch.float32),
-                    views=[self._out_views(big[i], small[i], B, H, W) for i in range(n)])
+                    views=[self._out_views(big[i], small[i], B, H, W) for i in range(n)], **extra)
 
-    def _half_loop(self, bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, single):
+    def _half_loop(self, bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, single, rgbd=None):
         """Generator: the COMPLETE inner loop of images [b0, b1) on stream `st` -- re-projection of their poses -> window
         lookup -> update block -> up-sampling -> descriptor weight -> LM step, n times (PoseRefiner.py:315-362).  Images are
         independent, so nothing synchronises the batch halves per iteration: each half runs its own loop on its own stream
@@ -293,37 +301,52 @@ class PoseRefiner(nn.Module):
             yield from eng.half_gen(self.cf_net.corr_fn, coords1, B, b0, b1, st, flow_up, single=single, induced=ic)
             ops.corr_weight(g1[b0:b1], g2[b0:b1], flow_up, depth[b0:b1], self.sigma[0], out=wmap)                      # :342-345
             yield
-            ops.lm_step(flow_up, wmap, depth[b0:b1], K[b0:b1], Gc, num_iters=opt, ep_lambda=ep_l, lm_lambda=lm_l,
-                        max_update=1.0, eps=EPS, out=(Gn, Hm, bv, xi, info), slot=b0)                                   # :349-356
+            if rgbd is None:
+                ops.lm_step(flow_up, wmap, depth[b0:b1], K[b0:b1], Gc, num_iters=opt, ep_lambda=ep_l, lm_lambda=lm_l,
+                            max_update=1.0, eps=EPS, out=(Gn, Hm, bv, xi, info), slot=b0)                               # :349-356
+            else:        # the same step with the 3-D residual of the observed depth
+                shared = rgbd["index"] is not None
+                ops.lm_step_rgbd(flow_up, wmap, depth[b0:b1], K[b0:b1], Gc, rgbd["obs"] if shared else rgbd["obs"][b0:b1],
+                                 rgbd["theta"][b0:b1], rgbd["K_obs"][b0:b1], rgbd["index"], num_iters=opt, ep_lambda=ep_l, lm_lambda=lm_l,
+                                 max_update=1.0, eps=EPS, out=(Gn, Hm, bv, xi, info, bufs["dstats"][i, b0:b1]), slot=b0,
+                                 index_rows=(b0, b1) if shared else None, **rgbd["params"])
             yield
             Gc = Gn
 
-    def _loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n):
+    def _loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
         """Eager launches of the n inner iterations -> (big, small); the batch halves' launches are issued alternately."""
         B, dev = depth.shape[0], depth.device
         eng = self.cf_net.engine()
-        bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev)
+        bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd)
         G3 = G.reshape(-1, 4, 4)
         hv = eng.halves(B)
         main = torch.cuda.current_stream()
         jobs = []
         for k, (b0, b1) in enumerate(hv):
             st = main if k == 0 else eng._stream(dev, k)
-            jobs.append((self._half_loop(bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, len(hv) == 1), st))
+            jobs.append((self._half_loop(bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd), st))
         eng.run_interleaved(jobs, main)
+        if rgbd is not None:
+            rgbd["stats"] = bufs["dstats"]
         return bufs["big"], bufs["small"]
 
-    def _inner_loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n):
+    def _inner_loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
         """-> list of n tuples (flow_up, wmap, G, Hm, bv, xi, info): eager launches, or one replayed hipGraph PER BATCH HALF
-        (each a linear chain on its own stream) per outer iteration."""
+        (each a linear chain on its own stream) per outer iteration.  rgbd (the depth term's inputs: obs, theta, K_obs, index,
+        params) receives `stats`, the (n,B,2) statistics; its tensors are inputs of the graph like depth and K."""
         B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
         unpack = lambda big, small: [self._out_views(big[i], small[i], B, H, W) for i in range(n)]
         if not self.use_graph or ops.profiling():
-            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n))
+            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd))
         eng = self.cf_net.engine()
         key = (depth.data_ptr(), K.data_ptr(), g1.data_ptr(), g2.data_ptr(), self.cf_net.corr_fn._buf.data_ptr(),
                tuple(depth.shape), n, self.cfg.OPTIM_ITER_COUNT, float(ep_l), float(lm_l), eng.buffer_key(), self._wkey)
-        skey = key[5:]                          # everything but the addresses: one record per shape
+        tail = 0
+        if rgbd is not None:                    # the depth term's configuration, then its addresses (last: the static key drops them)
+            ptrs = tuple(rgbd[k].data_ptr() for k in ("obs", "theta", "K_obs")) + (rgbd["index"].dev.data_ptr() if rgbd["index"] is not None else 0,)
+            key += ("rgbd", tuple(rgbd["obs"].shape), rgbd["index"] is not None, tuple(sorted(rgbd["params"].items()))) + ptrs
+            tail = len(ptrs)
+        skey = key[5:len(key) - tail]           # everything but the addresses: one record per shape
         rec = self._shapes.get(skey)
         if rec is None:
             if len(self._shapes) >= eng.MAX_SETS:      # as many shapes as the engine keeps activation buffer sets for
@@ -336,16 +359,16 @@ class PoseRefiner(nn.Module):
                 # the views keep moving (a renderer that allocates fresh tensors every outer iteration): re-capturing per
                 # pointer set would cost more than it saves.  Switch to ONE graph set over persistent input buffers and pay
                 # a device copy of depth / K / descriptors (~0.65 GB at 480x640, B=8: ~0.25 ms) per outer iteration.
-                sb = self._static_inputs(rec, depth, K, g1, g2)
-                stkey = ("static",) + key[4:]
+                sb = self._static_inputs(rec, depth, K, g1, g2, rgbd)
+                stkey = ("static",) + key[4:len(key) - tail]
                 gr = rec["static"]
                 if gr is None or gr["key"] != stkey:
-                    gr = rec["static"] = self._capture(stkey, sb["depth"], sb["K"], sb["g1"], sb["g2"], G, h, w, ep_l, lm_l, n)
+                    gr = rec["static"] = self._capture(stkey, sb["depth"], sb["K"], sb["g1"], sb["g2"], G, h, w, ep_l, lm_l, n, sb.get("rgbd"))
             else:
                 rec["captures"] += 1
-                gr = rec["gr"] = self._capture(key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n)
+                gr = rec["gr"] = self._capture(key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd)
         if gr is None:                         # capture refused: eager launches from now on (use_graph is off)
-            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n))
+            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd))
         gr["G"].copy_(G.reshape(-1, 4, 4))
         main = torch.cuda.current_stream()
         timing = self.loop_timing is not None          # measurement hook (tools/loop_overlap.py): when does each half run?
@@ -370,23 +393,36 @@ class PoseRefiner(nn.Module):
             self.loop_timing.append(marks)
         # the output buffers belong to the graph record and are overwritten by the next replay: the caller gets its own
         # copies (the reference returns distinct tensors per iteration): two device copies per OUTER iteration
+        if rgbd is not None:
+            rgbd["stats"] = gr["bufs"]["dstats"].clone()
         return unpack(gr["bufs"]["big"].clone(), gr["bufs"]["small"].clone())
 
-    def _static_inputs(self, rec, depth, K, g1, g2):
-        """Persistent copies (per shape record) of the per-outer-iteration inputs of the inner graph; refreshed when the sources change."""
-        shapes = (tuple(depth.shape), tuple(K.shape), tuple(g1.shape), tuple(g2.shape))
+    def _static_inputs(self, rec, depth, K, g1, g2, rgbd=None):
+        """Persistent copies (per shape record) of the per-outer-iteration inputs of the inner graph; refreshed when the sources change.
+        With the depth term: also of the observed depth, the crop maps, the full-frame intrinsics and the frame index (sb["rgbd"])."""
+        more = [] if rgbd is None else [rgbd["obs"], rgbd["theta"], rgbd["K_obs"]] + ([rgbd["index"].dev] if rgbd["index"] is not None else [])
+        shapes = (tuple(depth.shape), tuple(K.shape), tuple(g1.shape), tuple(g2.shape)) + tuple(tuple(t.shape) for t in more)
         sb = rec["sbuf"]
         if sb is None or sb["shapes"] != shapes:
             sb = rec["sbuf"] = dict(shapes=shapes, depth=torch.empty_like(depth), K=torch.empty_like(K),
-                                    g1=torch.empty_like(g1), g2=torch.empty_like(g2), src=None)
+                                    g1=torch.empty_like(g1), g2=torch.empty_like(g2), src=None, more=[torch.empty_like(t) for t in more])
             rec["static"] = None
-        src = (depth.data_ptr(), K.data_ptr(), g1.data_ptr(), g2.data_ptr(), depth._version, K._version, g1._version, g2._version)
+        src = (depth.data_ptr(), K.data_ptr(), g1.data_ptr(), g2.data_ptr(), depth._version, K._version, g1._version, g2._version) + \
+            tuple(t.data_ptr() for t in more) + tuple(t._version for t in more)
         if sb["src"] != src:
             sb["depth"].copy_(depth); sb["K"].copy_(K); sb["g1"].copy_(g1); sb["g2"].copy_(g2)
+            for dst, t in zip(sb["more"], more):
+                dst.copy_(t)
             sb["src"] = src
+        if rgbd is not None:
+            m = sb["more"]
+            index = ops.SourceIndex.from_device(m[3], rgbd["index"].host, rgbd["index"].S) if rgbd["index"] is not None else None
+            sb["rgbd"] = dict(obs=m[0], theta=m[1], K_obs=m[2], index=index, params=rgbd["params"])
+        else:
+            sb.pop("rgbd", None)
         return sb
 
-    def _capture(self, key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n):
+    def _capture(self, key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
         """-> graph record, or None when capture is refused (the caller then runs eager launches).  One hipGraph per batch
         half, each a LINEAR chain captured on the stream it will be replayed on: concurrency between the halves comes from
         the two streams, not from branches inside a graph (a two-branch graph of this length replayed almost serially on
@@ -401,10 +437,10 @@ class PoseRefiner(nn.Module):
             side = torch.cuda.Stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):                  # warm-up on a side stream: weight packing, allocator, caches
-                self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n)
+                self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, rgbd)
             main.wait_stream(side)
             eng.state_restore(snap)
-            bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev)
+            bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd)
             hv = eng.halves(B)
             graphs = []
             torch.cuda.synchronize()
@@ -415,7 +451,7 @@ class PoseRefiner(nn.Module):
                 graph = torch.cuda.CUDAGraph()
                 cap = torch.cuda.Stream()                  # (torch captures on a side stream of its own and replays on the current one)
                 with torch.cuda.graph(graph, stream=cap):
-                    for _ in self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1):
+                    for _ in self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd):
                         pass
                 graphs.append((graph, st))
             return dict(key=key, graphs=graphs, G=Gs, bufs=bufs)
@@ -430,8 +466,11 @@ class PoseRefiner(nn.Module):
 
     @torch.no_grad()
     def forward(self, image, Ts, intrinsics, fea_3d=None, Tj_gt=None, obj_cls=None, geofea_3d=None, geofea_2d=None,
-                image_index=None):
+                image_index=None, depth=None):
         """image (B,3,H0,W0); Ts SE3Sequence (B,1,4,4); intrinsics (B,3,3) -> dict (PoseRefiner.py:366-376).
+        depth (S,H0,W0) or (S,1,H0,W0): the OBSERVED depth of the frames `image` holds, in the meshes' unit (<= 0 or non-finite =
+        missing), indexed by the same image_index.  Used only by a refiner constructed with depth_term; the dict then has
+        `depth_stats` (B,2) fp64 of the last inner iteration: [pixels with a gated depth, sum v w omega |r3|^2].
         Several objects of one camera frame (mixed classes): image (S,3,H0,W0) and geofea_2d (S,32,H0,W0) with S <= B sources
         and image_index (B,) integers naming the source of every object; obj_cls names every object's class; fea_3d /
         geofea_3d are one tensor (one class for the whole batch), a list of B (P_b, C) tables, or None when the renderer
@@ -454,6 +493,19 @@ class PoseRefiner(nn.Module):
             ops.range_guard_arm(intrinsics.device)
         self._refresh()
         cfg = self.cfg
+        rgbd = None
+        if self.depth_term is not None and depth is not None:
+            if not self.fused:
+                raise NotImplementedError("depth_term needs the fused schedule (fused=True)")
+            obs = ops._chk(depth, "depth")
+            obs = obs[:, 0] if obs.dim() == 4 and obs.shape[1] == 1 else obs
+            S = image.shape[0] if image is not None else Ts.G.shape[0]
+            if obs.dim() != 3 or obs.shape[0] != S:
+                raise ValueError(f"depth must be ({S},H0,W0) or ({S},1,H0,W0), one map per source image; got {tuple(depth.shape)}")
+            if image_index is not None and not isinstance(image_index, ops.SourceIndex):
+                image_index = views_kw["image_index"] = ops.SourceIndex(image_index, S, obs.device)
+            rgbd = dict(obs=obs.contiguous(), K_obs=ops._chk(intrinsics, "intrinsics").reshape(-1, 3, 3), index=image_index,
+                        params=self.depth_term)
         lm_l, ep_l = cfg.get("LM_LMBDA", LM_LMBDA), cfg.get("EP_LMBDA", EP_LMBDA)
         Tij_gt, syn_imgs, syn_depths = [], [], []
         Ti = Ts
@@ -510,8 +562,12 @@ class PoseRefiner(nn.Module):
 
             loop = None
             if self.fused:      # all ITER_COUNT inner iterations of this outer iteration: one (replayable) unit
+                if rgbd is not None:
+                    if views.get("theta") is None:
+                        raise ValueError("depth_term: the renderer's views carry no `theta` (the crop maps); RendererAdapter provides it")
+                    rgbd["theta"] = views["theta"]
                 loop = self._inner_loop(syn_depth, intrinsics_crop, geofea1_crop, geofea2_crop, Tij.G, h, w, ep_l, lm_l,
-                                        cfg.ITER_COUNT)
+                                        cfg.ITER_COUNT, rgbd)
             for i in range(cfg.ITER_COUNT):
                 self.intrinsics_history.append(intrinsics_crop)
                 syn_depths.append(syn_depth)
@@ -543,6 +599,8 @@ class PoseRefiner(nn.Module):
 
         Ti = Tij * Ti                                                   # final update (:365)
         extra = {"occlusion_visible": views["occlusion_visible"]} if "occlusion_visible" in views else {}
+        if rgbd is not None:
+            extra["depth_stats"] = rgbd["stats"][-1]
         return {
             **extra,
             "Tij": Tij,

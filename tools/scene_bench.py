@@ -25,7 +25,14 @@ resolve with the resident tables).  Nothing is compared against a threshold.
 times the BOP pose-error functions of the frame at its initial poses: `HipEpoch.bop_metrics` (two z-buffer renders of the batch at the
 frame size, rnnpose_bop_vsd_f64, rnnpose_bop_sym_dist_f64 per class, the recalls on the host), `BOPEvaluator.errors` (the same without
 the copy back), the two entry points alone on ready depth images, and -- wall clock, on the host -- their numpy restatement
-tests/bop_ref.py on the same inputs.  Nothing is compared against a threshold."""
+tests/bop_ref.py on the same inputs.  Nothing is compared against a threshold.
+
+    python tools/scene_bench.py --depth [--out profiles/scene_bench_depth.json]
+
+measures the depth term of the LM step (PoseRefiner(depth_term=True)): `refine_frame` without (the parent's
+behaviour) and with the term on the frame's observed depth, alternating inside every run; and the step alone at the 240 x 240 crops of the
+initial poses -- ops.lm_step against ops.lm_step_rgbd on the same inputs, 50 launches per timed window.  Nothing is compared against a
+threshold."""
 from __future__ import annotations
 
 import argparse
@@ -103,6 +110,59 @@ def occlusion_bench(a, models, cfg, net, hip, items, given, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def depth_bench(a, models, cfg, net, hip, items, given, size, cover):
+    """--depth: refine_frame without and with the depth term; the LM step alone, plain and depth-aware"""
+    from rnnpose_amd import zoom
+    n, zs, reps = len(items), tuple(cfg.zoom_crop_size), 50
+    depth_dev = items[0].depth.cuda()
+    hip_on = ee.HipEpoch(models, cfg=cfg, desc2d=net, depth_term=True)
+    hip_on.refiner.load_state_dict(hip.refiner.state_dict())
+    with_depth = [ee.EvalItem(it.class_name, it.image, it.K, it.pose_init, it.pose_gt, it.geofea_2d, frame_id=it.frame_id, depth=depth_dev)
+                  for it in given]
+    whole = time_alternately({"off": lambda: hip.refine_frame(given), "on": lambda: hip_on.refine_frame(with_depth)}, a.runs, a.warmup)
+    stats = hip_on.last_depth_stats.cpu()
+    # the step alone: the crops of the initial poses, zero flow, weight 1 on the rendered object, one Gauss-Newton step from the identity
+    ren, names = hip.renderer, [it.class_name for it in items]
+    T0 = torch.as_tensor(np.stack([it.pose_init for it in items]).astype(np.float32)).cuda()
+    K = torch.as_tensor(np.stack([it.K for it in items]).astype(np.float32)).cuda()
+    pc = ren.render_pointcloud(names, T=T0, K=K, render_image_size=size)
+    _, K_crop, theta = zoom.gen_zoom_crop_grids(pc, K, T0, [n, 1, *zs], margin_ratio=0.4, want_grids=False)
+    _, syn_depth = ren(names, None, T=T0, K=K_crop, render_image_size=zs, render_tex=True)
+    syn_depth = syn_depth.clamp(min=0).contiguous()
+    flow = torch.zeros(n, 2, *zs, device="cuda")
+    wgt = (syn_depth[:, 0] > 0).float().contiguous()
+    G = torch.eye(4, device="cuda").repeat(n, 1, 1)
+    obs, idx = depth_dev[None].contiguous(), ops.SourceIndex([0] * n, 1, "cuda")
+    plain_out = tuple(torch.empty_like(x) for x in ops.lm_step(flow, wgt, syn_depth, K_crop, G))
+    rgbd_out = tuple(torch.empty_like(x) for x in ops.lm_step_rgbd(flow, wgt, syn_depth, K_crop, G, obs, theta, K, idx))
+
+    def plain():
+        for _ in range(reps):
+            ops.lm_step(flow, wgt, syn_depth, K_crop, G, out=plain_out)
+
+    def rgbd():
+        for _ in range(reps):
+            ops.lm_step_rgbd(flow, wgt, syn_depth, K_crop, G, obs, theta, K, idx, out=rgbd_out)
+    alone = time_alternately({"lm_step": plain, "lm_step_rgbd": rgbd}, a.runs, a.warmup)
+    med = lambda r, k: r[k]["median_ms"]
+    us = {k: med(alone, k) * 1e3 / reps for k in alone}
+    added = med(whole, "on") - med(whole, "off")
+    steps = cfg.RENDER_ITER_COUNT * cfg.ITER_COUNT * cfg.OPTIM_ITER_COUNT
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=list(size), crop=list(zs), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               frame_coverage=cover, runs=a.runs, warmup=a.warmup, depth_term=dict(ops.DEPTH_TERM_DEFAULTS), refine_frame=whole, added_ms=added,
+               added_share=added / med(whole, "off"), lm_steps_per_refinement=steps, step_alone=alone, launches_per_window=reps, us_per_step=us,
+               step_ratio=us["lm_step_rgbd"] / us["lm_step"], active_pixels_last_step=[float(v) for v in stats[:, 0]],
+               depth_cost_last_step=[float(v) for v in stats[:, 1]],
+               note="refine_frame off = the parent's behaviour, timed alternately with on in every run; the step alone: back-to-back eager "
+                    "launches on one stream (launch overhead included in both), batch = the frame's objects; nothing is compared against a "
+                    "threshold")
+    print(f"refine_frame off {med(whole, 'off'):8.2f} ms   on {med(whole, 'on'):8.2f} ms   added {added:+.3f} ms ({res['added_share']:+.2%}) over {steps} LM steps")
+    print(f"  step alone at B = {n}, {zs[0]} x {zs[1]}: lm_step {us['lm_step']:.1f} us   lm_step_rgbd {us['lm_step_rgbd']:.1f} us   ratio {res['step_ratio']:.2f}")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def bop_bench(a, models, hip, items, size, cover):
     """--bop: the BOP errors of the frame's objects at their initial poses"""
     import time
@@ -166,6 +226,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--occlusion", action="store_true", help="measure the occlusion mask between the objects instead (see above)")
     ap.add_argument("--bop", action="store_true", help="time the BOP pose-error functions of the frame instead (see above)")
+    ap.add_argument("--depth", action="store_true", help="measure the depth term of the LM step instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -185,6 +246,8 @@ def main():
         return bop_bench(a, models, hip, items, (H, W), cover)
     if a.occlusion:
         return occlusion_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
+    if a.depth:
+        return depth_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
     per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
     whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
