@@ -7,8 +7,10 @@
 // upper-triangle + 6 right-hand-side sums in fp64 over a strided set of pixels, a wave64 shuffle tree and
 // one LDS hop reduce the workgroup, and per-workgroup partials are summed in FIXED order by the solve
 // kernel (deterministic: no atomics).  HBM traffic = target + weight + depth read once (16 B/pixel).
-//   lm_rgbd_eq      the same sums with an opt-in 3-D residual from the OBSERVED depth of an RGB-D camera (no counterpart in the reference;
+//   lm_rgbd_eq     the same sums with an opt-in 3-D residual from the OBSERVED depth of an RGB-D camera (no counterpart in the reference;
 //                  include/rnnpose_hip.h): + four gathered taps per pixel
+// ONE kernel, lm_eq_kernel<DEPTH, FUSED>, in two instantiation families: DEPTH = false the plain step, DEPTH = true the depth-aware
+// one; one launch path, launch_lm_iteration, and one checked loop, lm_run, under all LM entries.
 #include <cmath>
 
 #include "geometry.cuh"
@@ -65,7 +67,7 @@ struct LmTail {
   float* xi;
   int* info;
   double ep, lm, max_update;
-  double* dstats;               // (B,2) depth-term statistics of lm_rgbd_eq_kernel, or null (always null for lm_normal_eq_kernel)
+  double* dstats;               // (B,2) depth-term statistics of lm_eq_kernel<true, .>, or null (always null for the plain kernel)
 };
 __device__ void lm_finalize_block_one(const double* __restrict__ partials, int nblk, int b, double* __restrict__ Hm, double* __restrict__ bv,
                                       double* __restrict__ dstats);
@@ -113,7 +115,7 @@ __device__ __forceinline__ void lm_accumulate(double (&acc)[NA], float wgt, floa
 }
 
 // the workgroup's 27 sums -> its partial record; FUSED: the last workgroup of the image finalizes, solves and updates the pose
-// NA = NACC, or NACC_RGBD for lm_rgbd_eq_kernel: its two statistics ride in slots 27 and 28 of the same 32-slot butterfly and record
+// NA = NACC, or NACC_RGBD for lm_eq_kernel<true, .>: its two statistics ride in slots 27 and 28 of the same 32-slot butterfly and record
 template <bool FUSED, int NA = NACC>
 __device__ __forceinline__ void lm_reduce_tail(double (&acc)[NA], double* __restrict__ partials, const LmTail& tail, int b, int nblk, int bx) {
   static_assert(NA <= PSTRIDE, "the partial record has 32 slots");
@@ -173,63 +175,6 @@ __device__ __forceinline__ void lm_reduce_tail(double (&acc)[NA], double* __rest
     __syncthreads();
     if (threadIdx.x == 0) lm_solve_one(tail.Hm, tail.bv, tail.G_in, b, tail.ep, tail.lm, tail.max_update, tail.G_out, tail.xi, tail.info);
   }
-}
-
-template <bool FUSED>
-__global__ __launch_bounds__(LM_THREADS) void lm_normal_eq_kernel(const float* __restrict__ target, int target_mode,
-                                                                  const float* __restrict__ weight,
-                                                                  const float* __restrict__ depth, float eps,
-                                                                  const float* __restrict__ K,
-                                                                  const float* __restrict__ G, int H, int W,
-                                                                  double* __restrict__ partials, const LmTail tail) {
-  const int b = blockIdx.y;
-  const int nblk = gridDim.x;
-  const long long P = static_cast<long long>(H) * W;
-  const Intr k = rp::load_intr(K, b);
-  const Pose g = rp::load_pose(G, b);
-  double acc[NACC];
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
-
-  // LM_BATCH pixels per trip: their 4-5 loads each are issued (unconditionally, clamped to the last pixel) before the
-  // first fp64 chain starts.  One pixel per trip was 8 dependent memory round trips per thread: 26 us per launch for
-  // 20 MB (r02).  Pixels are accumulated in the same order as before, so the partial sums are bit-identical.
-  const long long stride = static_cast<long long>(nblk) * LM_THREADS;
-  for (long long t0 = static_cast<long long>(blockIdx.x) * LM_THREADS + threadIdx.x; t0 < P; t0 += LM_BATCH * stride) {
-    float wgt_[LM_BATCH], dep_[LM_BATCH], tx_[LM_BATCH], ty_[LM_BATCH];
-#pragma unroll
-    for (int j = 0; j < LM_BATCH; ++j) {
-      const long long tj = t0 + j * stride;
-      const long long t = tj < P ? tj : P - 1;
-      wgt_[j] = weight[b * P + t];
-      dep_[j] = depth[b * P + t];
-      if (target_mode == 0) {
-        const float2 tt = *reinterpret_cast<const float2*>(target + (b * P + t) * 2);
-        tx_[j] = tt.x;
-        ty_[j] = tt.y;
-      } else {
-        tx_[j] = target[(static_cast<long long>(b) * 2 + 0) * P + t];
-        ty_[j] = target[(static_cast<long long>(b) * 2 + 1) * P + t];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < LM_BATCH; ++j) {
-      const long long t = t0 + j * stride;
-      if (t >= P) break;
-      const unsigned tu = static_cast<unsigned>(t);            // t < H*W < 2^31: 32-bit division (64-bit is a software routine)
-      const int y = static_cast<int>(tu / static_cast<unsigned>(W)), x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
-      const float wgt = wgt_[j];
-      // zero-weight pixels (the descriptor weight is 0 on the rendered background) add w * (...) = 0 to every sum: a wave
-      // made of such pixels skips the fp64 chain -- but only pixels whose target and depth are FINITE count as skippable: in the
-      // reference 0 * NaN = NaN poisons the system and the NaN -> zero-update guard fires (geometry/cholesky.py:43-44); a
-      // lane with a non-finite input keeps its wave in the chain, so that happens here too, whatever the wave is made of.
-      const bool skippable = wgt == 0.f && __builtin_isfinite(tx_[j]) && __builtin_isfinite(ty_[j]) && __builtin_isfinite(dep_[j]);
-      if (__builtin_amdgcn_ballot_w64(!skippable) == 0ull) continue;
-      lm_accumulate(acc, wgt, dep_[j], tx_[j], ty_[j], x, y, target_mode, eps, k, g);
-    }
-  }
-  lm_reduce_tail<FUSED>(acc, partials, tail, b, nblk, static_cast<int>(blockIdx.x));
 }
 
 // ---- the depth-aware step (RGB-D): an opt-in 3-D residual from the OBSERVED depth in the same 27 sums -------------------------------
@@ -335,21 +280,61 @@ __device__ __forceinline__ void lm_accumulate_depth(double (&acc)[NACC_RGBD], do
   acc[28] += s * (rx * rx + ry * ry + rz * rz);
 }
 
-// lm_normal_eq_kernel with the depth term: the same trips, the same order of the 2-D sums (lm_accumulate itself), the same tail.  The
-// four depth taps of a trip's LM_BATCH pixels are a SECOND batch of loads, issued together once the targets have arrived.
-template <bool FUSED>
-__global__ __launch_bounds__(LM_THREADS) void lm_rgbd_eq_kernel(const float* __restrict__ target, int target_mode,
-                                                                const float* __restrict__ weight, const float* __restrict__ depth,
-                                                                float eps, const float* __restrict__ K, const float* __restrict__ G,
-                                                                int H, int W, const LmDepthTerm dt, double* __restrict__ partials,
-                                                                const LmTail tail) {
+struct LmGate {                 // one pixel's gate decision, and what its depth term is built from
+  rp::Reproj r;
+  bool valid, active;
+  float Yx, Yy, Yz;
+};
+
+// the gate of one pixel (fp32, no fp64 chain): the observed point from the taps and whether the depth term is active there
+__device__ __forceinline__ LmGate lm_depth_gate(float dep, float tx, float ty, int x, int y, int target_mode, float eps, const Intr& k, const Pose& g,
+                                                int H, int W, const LmFrame& f, const float (&z)[4], const LmDepthTerm& dt) {
+  LmGate q;
+  q.r = rp::reproject(dep + eps, static_cast<float>(x), static_cast<float>(y), k, g);
+  q.valid = (q.r.Z0 > rp::kMinDepthValid) && (q.r.Z1 > rp::kMinDepthValid);
+  float ix, iy;
+  lm_obs_position(tx, ty, x, y, target_mode, H, W, f, ix, iy);
+  const bool has = lm_obs_point(ix, iy, z, f, dt.edge_tol, q.Yx, q.Yy, q.Yz);
+  q.active = has && q.valid && fabsf(q.Yz - q.r.Z1) <= dt.gate;
+  return q;
+}
+
+// the depth term of one pixel behind the 2-D term: scale omega, then the sums of an ACTIVE pixel
+__device__ __forceinline__ void lm_depth_step(double (&acc)[NACC_RGBD], const LmGate& q, float wgt, float depth_weight, const Intr& k) {
+  const bool tiny = q.r.Zc <= rp::kMinDepthProj + 0.01f;
+  const float zi2 = tiny ? 0.f : 1.0f / (q.r.Zc * q.r.Zc);
+  const float omega = depth_weight * (k.fx * k.fy) * zi2;
+  const double s = (q.valid ? static_cast<double>(wgt) : 0.0) * static_cast<double>(omega);
+  // a pixel without a measurement, outside the gate or with a zero scale adds NOTHING: with depth_weight = 0 or an empty observed
+  // depth the 27 sums are the plain step's bit for bit
+  if (q.active && s != 0.0) lm_accumulate_depth(acc, s, q.r.X1, q.r.Y1, q.r.Z1, q.Yx, q.Yy, q.Yz);
+}
+
+// crop pixel t -> (x, y).  t < H*W < 2^31: 32-bit division (64-bit is a software routine)
+__device__ __forceinline__ void lm_pixel_xy(long long t, int W, int& x, int& y) {
+  const unsigned tu = static_cast<unsigned>(t);
+  y = static_cast<int>(tu / static_cast<unsigned>(W));
+  x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
+}
+
+// ---- the ONE normal-equation kernel: trips, loads, skip, 2-D sums and tail; DEPTH adds the depth term at four sites -----------------------
+// DEPTH = false is the plain step, DEPTH = true the depth-aware one (dt is read by it alone): the same trips, the same order of the 2-D
+// sums (lm_accumulate itself), the same tail, so that the depth-aware step with its term off IS the plain step.  The kernel itself is
+// the template: the same body as a device function under two thin kernels is optimised before it is inlined, outside a kernel's
+// launch bounds, and comes out with the trip's loads and waits arranged otherwise (tests/test_isa_guard.py refuses that form).
+template <bool DEPTH, bool FUSED>
+__global__ __launch_bounds__(LM_THREADS) void lm_eq_kernel(const float* __restrict__ target, int target_mode, const float* __restrict__ weight,
+                                                           const float* __restrict__ depth, float eps, const float* __restrict__ K,
+                                                           const float* __restrict__ G, int H, int W, const LmDepthTerm dt,
+                                                           double* __restrict__ partials, const LmTail tail) {
+  constexpr int NA = DEPTH ? NACC_RGBD : NACC;
   const int b = blockIdx.y;
   const int nblk = gridDim.x;
   const long long P = static_cast<long long>(H) * W;
   const Intr k = rp::load_intr(K, b);
   const Pose g = rp::load_pose(G, b);
-  LmFrame f;
-  {
+  LmFrame f{};
+  if constexpr (DEPTH) {
     const int s = dt.src_index ? dt.src_index[b] : b;
     f.ok = s >= 0 && s < dt.S;                                       // (the caller has refused it on the host; the second fence)
     f.obs = dt.obs + static_cast<long long>(f.ok ? s : 0) * dt.Ho * dt.Wo;
@@ -359,10 +344,13 @@ __global__ __launch_bounds__(LM_THREADS) void lm_rgbd_eq_kernel(const float* __r
     f.Ho = dt.Ho;
     f.Wo = dt.Wo;
   }
-  double acc[NACC_RGBD];
+  double acc[NA];
 #pragma unroll
-  for (int i = 0; i < NACC_RGBD; ++i) acc[i] = 0.0;
+  for (int i = 0; i < NA; ++i) acc[i] = 0.0;
 
+  // LM_BATCH pixels per trip: their 4-5 loads each are issued (unconditionally, clamped to the last pixel) before the
+  // first fp64 chain starts.  One pixel per trip was 8 dependent memory round trips per thread: 26 us per launch for
+  // 20 MB (r02).  Pixels are accumulated in the same order as before, so the partial sums are bit-identical.
   const long long stride = static_cast<long long>(nblk) * LM_THREADS;
   for (long long t0 = static_cast<long long>(blockIdx.x) * LM_THREADS + threadIdx.x; t0 < P; t0 += LM_BATCH * stride) {
     float wgt_[LM_BATCH], dep_[LM_BATCH], tx_[LM_BATCH], ty_[LM_BATCH];
@@ -382,59 +370,56 @@ __global__ __launch_bounds__(LM_THREADS) void lm_rgbd_eq_kernel(const float* __r
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // second batch: the taps, unconditionally and at positions clamped into the frame (lm_obs_point decides which of them count).  Only the
-    // taps stay live across the loads: (ix, iy) are formed again behind them -- keeping 16 more registers took the kernel to 1 wave per SIMD
-    float z_[LM_BATCH][4];
+    // DEPTH, second batch: the four depth taps of the trip's pixels, issued together once the targets have arrived, unconditionally and at
+    // positions clamped into the frame (lm_obs_point decides which of them count).  Only the taps stay live across the loads: (ix, iy)
+    // are formed again behind them -- keeping 16 more registers took the kernel to 1 wave per SIMD
+    float z_[DEPTH ? LM_BATCH : 1][4];
+    if constexpr (DEPTH) {
 #pragma unroll
-    for (int j = 0; j < LM_BATCH; ++j) {
-      const long long tj = t0 + j * stride;
-      const unsigned tu = static_cast<unsigned>(tj < P ? tj : P - 1);
-      const int y = static_cast<int>(tu / static_cast<unsigned>(W)), x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
-      float ix, iy;
-      lm_obs_position(tx_[j], ty_[j], x, y, target_mode, H, W, f, ix, iy);
-      int x0, y0;
-      lm_obs_corner(ix, iy, x0, y0);
-      const int xa = min(max(x0, 0), f.Wo - 1), xb = min(max(x0 + 1, 0), f.Wo - 1);
-      const int ya = min(max(y0, 0), f.Ho - 1) * f.Wo, yb = min(max(y0 + 1, 0), f.Ho - 1) * f.Wo;
-      z_[j][0] = f.obs[ya + xa];
-      z_[j][1] = f.obs[ya + xb];
-      z_[j][2] = f.obs[yb + xa];
-      z_[j][3] = f.obs[yb + xb];
+      for (int j = 0; j < LM_BATCH; ++j) {
+        const long long tj = t0 + j * stride;
+        int x, y, x0, y0;
+        lm_pixel_xy(tj < P ? tj : P - 1, W, x, y);
+        float ix, iy;
+        lm_obs_position(tx_[j], ty_[j], x, y, target_mode, H, W, f, ix, iy);
+        lm_obs_corner(ix, iy, x0, y0);
+        const int xa = min(max(x0, 0), f.Wo - 1), xb = min(max(x0 + 1, 0), f.Wo - 1);
+        const int ya = min(max(y0, 0), f.Ho - 1) * f.Wo, yb = min(max(y0 + 1, 0), f.Ho - 1) * f.Wo;
+        z_[j][0] = f.obs[ya + xa];
+        z_[j][1] = f.obs[ya + xb];
+        z_[j][2] = f.obs[yb + xa];
+        z_[j][3] = f.obs[yb + xb];
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < LM_BATCH; ++j) {
       const long long t = t0 + j * stride;
       if (t >= P) break;
-      const unsigned tu = static_cast<unsigned>(t);
-      const int y = static_cast<int>(tu / static_cast<unsigned>(W)), x = static_cast<int>(tu - static_cast<unsigned>(y) * static_cast<unsigned>(W));
+      int x, y;
+      lm_pixel_xy(t, W, x, y);
       const float wgt = wgt_[j];
-      // the gate is evaluated for EVERY pixel (fp32, no fp64 chain): the count of active pixels does not depend on the weights
-      const rp::Reproj r = rp::reproject(dep_[j] + eps, static_cast<float>(x), static_cast<float>(y), k, g);
-      const bool valid = (r.Z0 > rp::kMinDepthValid) && (r.Z1 > rp::kMinDepthValid);
-      float Yx, Yy, Yz, ix, iy;
-      lm_obs_position(tx_[j], ty_[j], x, y, target_mode, H, W, f, ix, iy);
-      const bool has = lm_obs_point(ix, iy, z_[j], f, dt.edge_tol, Yx, Yy, Yz);
-      const bool active = has && valid && fabsf(Yz - r.Z1) <= dt.gate;
-      acc[27] += active ? 1.0 : 0.0;
-      // the zero-weight-wave skip of lm_normal_eq_kernel, unchanged (a zero weight zeroes the depth term's sums as well)
+      LmGate q;
+      if constexpr (DEPTH) {
+        // the gate is evaluated for EVERY pixel, before the skip: the count of active pixels does not depend on the weights
+        q = lm_depth_gate(dep_[j], tx_[j], ty_[j], x, y, target_mode, eps, k, g, H, W, f, z_[j], dt);
+        acc[27] += q.active ? 1.0 : 0.0;
+      }
+      // zero-weight pixels (the descriptor weight is 0 on the rendered background) add w * (...) = 0 to every sum, the depth term's
+      // included: a wave made of such pixels skips the fp64 chain -- but only pixels whose target and depth are FINITE count as skippable: in the
+      // reference 0 * NaN = NaN poisons the system and the NaN -> zero-update guard fires (geometry/cholesky.py:43-44); a
+      // lane with a non-finite input keeps its wave in the chain, so that happens here too, whatever the wave is made of.
       const bool skippable = wgt == 0.f && __builtin_isfinite(tx_[j]) && __builtin_isfinite(ty_[j]) && __builtin_isfinite(dep_[j]);
       if (__builtin_amdgcn_ballot_w64(!skippable) == 0ull) continue;
       lm_accumulate(acc, wgt, dep_[j], tx_[j], ty_[j], x, y, target_mode, eps, k, g);
-      const bool tiny = r.Zc <= rp::kMinDepthProj + 0.01f;
-      const float zi2 = tiny ? 0.f : 1.0f / (r.Zc * r.Zc);
-      const float omega = dt.weight * (k.fx * k.fy) * zi2;
-      const double s = (valid ? static_cast<double>(wgt) : 0.0) * static_cast<double>(omega);
-      // a pixel without a measurement, outside the gate or with a zero scale adds NOTHING: with depth_weight = 0 or an empty observed
-      // depth the 27 sums are lm_normal_eq_kernel's bit for bit
-      if (active && s != 0.0) lm_accumulate_depth(acc, s, r.X1, r.Y1, r.Z1, Yx, Yy, Yz);
+      if constexpr (DEPTH) lm_depth_step(acc, q, wgt, dt.weight, k);
     }
   }
-  lm_reduce_tail<FUSED, NACC_RGBD>(acc, partials, tail, b, nblk, static_cast<int>(blockIdx.x));
+  lm_reduce_tail<FUSED, NA>(acc, partials, tail, b, nblk, static_cast<int>(blockIdx.x));
 }
 
 // sums the block partials in fixed order and expands to full H (6x6) and b (6)
-// dstats != null (lm_rgbd_eq_kernel's records only: the plain kernel never writes slots 27, 28): the two depth-term statistics too
+// dstats != null (lm_eq_kernel<true, .>'s records only: the plain kernel never writes slots 27, 28): the two depth-term statistics too
 __device__ void lm_finalize_block_one(const double* __restrict__ partials, int nblk, int b, double* __restrict__ Hm,
                                       double* __restrict__ bv, double* __restrict__ dstats) {
   // 8 groups of 32 lanes walk the partial records with stride 8 (each load is one coalesced 256-byte record), then
@@ -518,7 +503,6 @@ __device__ void mat4_mul(const float* A, const float* Bm, float* C) {
     }
 }
 
-// one thread per image: damping, Cholesky, substitutions, guards, exp, left increment
 // damping, 6x6 Cholesky solve, NaN -> 0, clamp, SE(3) exponential and left increment of image b (one thread)
 __device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv, const float* G, int b, double ep, double lm,
                                              double max_update, float* G_new /* may alias G */, float* xi_out, int* info) {
@@ -664,58 +648,54 @@ __global__ void se3_outer_update_kernel(const float* __restrict__ Tij, const flo
 // workspace = [B arrival counters, 8 bytes each: zero between launches][partial records]
 inline double* lm_partials(void* workspace, int B) { return static_cast<double*>(workspace) + B; }
 
-// per-workgroup partial sums into `workspace`; -> number of partial records per image
-int launch_normal_eq_partials(const float* target, int target_mode, const float* weight, const float* depth, float eps,
-                              const float* K, const float* G, int B, int H, int W, void* workspace, hipStream_t st) {
-  const long long P = static_cast<long long>(H) * W;
-  const int nblk = lm_blocks_per_image(P);
-  hipLaunchKernelGGL(lm_normal_eq_kernel<false>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps,
-                     K, G, H, W, lm_partials(workspace, B), LmTail{});
+// what every entry that builds the normal equations reads: the 2-D term's inputs, the crop size, the workspace
+struct LmInputs {
+  const float* target;
+  int target_mode;
+  const float* weight;
+  const float* depth;
+  float eps;
+  const float* K;
+  int B, H, W;
+  void* workspace;
+  size_t workspace_bytes;
+};
+
+// where an iteration writes and what its solve needs (G_in is set per iteration); G_out == null: no solve, the normal-equation entries
+LmTail lm_tail(void* workspace, double* Hm, double* bv, float* G_out, float* xi, int* info, double ep, double lm, double max_update,
+               double* dstats) {
+  LmTail tail{};
+  tail.tickets = static_cast<int*>(workspace);
+  tail.Hm = Hm; tail.bv = bv; tail.G_out = G_out; tail.xi = xi; tail.info = info;
+  tail.ep = ep; tail.lm = lm; tail.max_update = max_update; tail.dstats = dstats;
+  return tail;
+}
+
+// per-workgroup partial sums of the pose tail.G_in into the workspace (FUSED: and the tail); dt: the depth term, or null for the plain
+// step; -> number of partial records per image
+template <bool FUSED>
+int launch_lm_eq(const LmInputs& in, const LmDepthTerm* dt, const LmTail& tail, hipStream_t st) {
+  const int nblk = lm_blocks_per_image(static_cast<long long>(in.H) * in.W);
+  const auto kernel = dt ? lm_eq_kernel<true, FUSED> : lm_eq_kernel<false, FUSED>;
+  hipLaunchKernelGGL(kernel, dim3(nblk, in.B), dim3(LM_THREADS), 0, st, in.target, in.target_mode, in.weight, in.depth, in.eps, in.K,
+                     tail.G_in, in.H, in.W, dt ? *dt : LmDepthTerm{}, lm_partials(in.workspace, in.B), tail);
   return nblk;
 }
 
-// partial sums + (in the last-arriving workgroup of every image) finalize, damped solve, pose update: ONE launch per LM step
-void launch_lm_step_fused(const float* target, int target_mode, const float* weight, const float* depth, float eps, const float* K,
-                          const float* G_in, float* G_out, int B, int H, int W, double ep, double lm, double max_update,
-                          void* workspace, double* Hm, double* bv, float* xi, int* info, hipStream_t st) {
-  const long long P = static_cast<long long>(H) * W;
-  const int nblk = lm_blocks_per_image(P);
-  LmTail tail{};
-  tail.tickets = static_cast<int*>(workspace);
-  tail.Hm = Hm; tail.bv = bv; tail.G_in = G_in; tail.G_out = G_out; tail.xi = xi; tail.info = info;
-  tail.ep = ep; tail.lm = lm; tail.max_update = max_update;
-  hipLaunchKernelGGL(lm_normal_eq_kernel<true>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps,
-                     K, G_in, H, W, lm_partials(workspace, B), tail);
-}
-
-int launch_normal_eq(const float* target, int target_mode, const float* weight, const float* depth, float eps,
-                     const float* K, const float* G, int B, int H, int W, void* workspace, double* Hm, double* bv,
-                     hipStream_t st) {
-  const int nblk = launch_normal_eq_partials(target, target_mode, weight, depth, eps, K, G, B, H, W, workspace, st);
-  hipLaunchKernelGGL(lm_finalize_kernel, dim3(B), dim3(256), 0, st, lm_partials(workspace, B), nblk, Hm, bv, static_cast<double*>(nullptr));
-  return 0;
-}
-
-// the depth-aware step: partial sums (+ fused tail), or partial sums, finalize (with the statistics) and solve as three launches
-void launch_lm_rgbd(bool fused, const float* target, int target_mode, const float* weight, const float* depth, float eps, const float* K,
-                    const float* G_in, float* G_out, int B, int H, int W, const LmDepthTerm& dt, double ep, double lm, double max_update,
-                    void* workspace, double* Hm, double* bv, float* xi, int* info, double* dstats, hipStream_t st) {
-  const long long P = static_cast<long long>(H) * W;
-  const int nblk = lm_blocks_per_image(P);
+// ONE LM iteration.  fused: partial sums + (in the last-arriving workgroup of every image) finalize, damped solve, pose update as ONE
+// launch; else partial sums, finalize (with the statistics, given tail.dstats) and -- given tail.G_out -- the solve as three launches
+void launch_lm_iteration(bool fused, const LmInputs& in, const LmDepthTerm* dt, const LmTail& tail, hipStream_t st) {
   if (fused) {
-    LmTail tail{};
-    tail.tickets = static_cast<int*>(workspace);
-    tail.Hm = Hm; tail.bv = bv; tail.G_in = G_in; tail.G_out = G_out; tail.xi = xi; tail.info = info;
-    tail.ep = ep; tail.lm = lm; tail.max_update = max_update; tail.dstats = dstats;
-    hipLaunchKernelGGL(lm_rgbd_eq_kernel<true>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps, K, G_in,
-                       H, W, dt, lm_partials(workspace, B), tail);
+    launch_lm_eq<true>(in, dt, tail, st);
     return;
   }
-  hipLaunchKernelGGL(lm_rgbd_eq_kernel<false>, dim3(nblk, B), dim3(LM_THREADS), 0, st, target, target_mode, weight, depth, eps, K, G_in,
-                     H, W, dt, lm_partials(workspace, B), LmTail{});
-  hipLaunchKernelGGL(lm_finalize_kernel, dim3(B), dim3(256), 0, st, lm_partials(workspace, B), nblk, Hm, bv, dstats);
-  if (G_out)
-    hipLaunchKernelGGL(lm_solve_update_kernel, dim3(rp::cdiv(B, 64)), dim3(64), 0, st, Hm, bv, G_in, B, ep, lm, max_update, G_out, xi, info);
+  const int nblk = launch_lm_eq<false>(in, dt, tail, st);
+  hipLaunchKernelGGL(lm_finalize_kernel, dim3(in.B), dim3(256), 0, st, lm_partials(in.workspace, in.B), nblk, tail.Hm, tail.bv, tail.dstats);
+  // (G_in may alias G_out: each thread reads its whole pose before writing it.  A merged finalize + solve kernel was measured
+  //  SLOWER, 26 us vs 7 + 6 us: the solve is a serial fp64 chain that then waits behind the 256-thread reduction's launch)
+  if (tail.G_out)
+    hipLaunchKernelGGL(lm_solve_update_kernel, dim3(rp::cdiv(in.B, 64)), dim3(64), 0, st, tail.Hm, tail.bv, tail.G_in, in.B, tail.ep, tail.lm,
+                       tail.max_update, tail.G_out, tail.xi, tail.info);
 }
 
 }  // namespace
@@ -736,18 +716,6 @@ int rnnpose_lm_fused_tail(int enable) {          // measurement switch: 0 = thre
   return 0;
 }
 
-int rnnpose_lm_normal_eq_f64(const float* target, int target_mode, const float* weight, const float* depth,
-                             float depth_eps, const float* K, const float* G, int B, int H, int W, void* workspace,
-                             size_t workspace_bytes, double* Hm, double* bv, rnnpose_stream_t stream) {
-  const char* fn = "rnnpose_lm_normal_eq_f64";
-  RP_REQUIRE(target && weight && depth && K && G && workspace && Hm && bv, fn, "null pointer");
-  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
-  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31), fn, "bad size");
-  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
-  launch_normal_eq(target, target_mode, weight, depth, depth_eps, K, G, B, H, W, workspace, Hm, bv, rp::as_stream(stream));
-  return rp::check_launch(fn);
-}
-
 int rnnpose_lm_solve_update_f32(const double* Hm, const double* bv, const float* G, int B, double ep_lambda,
                                 double lm_lambda, double max_update, float* G_new, float* xi, int* info,
                                 rnnpose_stream_t stream) {
@@ -759,37 +727,60 @@ int rnnpose_lm_solve_update_f32(const double* Hm, const double* bv, const float*
   return rp::check_launch(fn);
 }
 
-static int lm_step_impl(const char* fn, const float* target, int target_mode, const float* weight, const float* depth,
-                        float depth_eps, const float* K, const float* G_in, float* G_out, int B, int H, int W, int num_iters,
-                        double ep_lambda, double lm_lambda, double max_update, void* workspace, size_t workspace_bytes,
-                        double* Hm, double* bv, float* xi, int* info, rnnpose_stream_t stream) {
-  RP_REQUIRE(target && weight && depth && K && G_in && G_out && workspace && Hm && bv && xi, fn, "null pointer");
-  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
-  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31) && num_iters >= 0, fn, "bad size");
-  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
+// the depth arguments of the two RGB-D entries
+static int lm_rgbd_check(const char* fn, const LmDepthTerm& dt, int B) {
+  RP_REQUIRE(dt.obs && dt.theta && dt.K_obs, fn, "null obs_depth / theta / K_obs");
+  RP_REQUIRE(dt.S >= 1 && dt.Ho > 0 && dt.Wo > 0 && static_cast<long long>(dt.Ho) * dt.Wo < (1LL << 31), fn,
+             "bad observed-frame size (S >= 1, Ho, Wo > 0)");
+  RP_REQUIRE(dt.src_index || dt.S == B, fn, "src_index is null: the observed depth must hold one frame per object (S == B)");
+  RP_REQUIRE(std::isfinite(dt.weight) && dt.weight >= 0.f, fn, "depth_weight must be finite and >= 0");
+  RP_REQUIRE(std::isfinite(dt.gate) && dt.gate >= 0.f, fn, "depth_gate must be finite and >= 0");
+  RP_REQUIRE(std::isfinite(dt.edge_tol) && dt.edge_tol >= 0.f, fn, "edge_tol must be finite and >= 0");
+  return 0;
+}
+
+// the arguments the LM entries share, in the order every entry tests them.  solve: a step entry (G_out and xi are outputs, num_iters
+// counts); need_iter: its G_out is written by an iteration only; dt: the depth arguments, tested before the workspace
+static int lm_check(const char* fn, const LmInputs& in, const LmDepthTerm* dt, const float* G_in, const LmTail& out, bool solve, int num_iters,
+                    bool need_iter) {
+  RP_REQUIRE(in.target && in.weight && in.depth && in.K && G_in && in.workspace && out.Hm && out.bv && (!solve || (out.G_out && out.xi)), fn,
+             "null pointer");
+  RP_REQUIRE(in.target_mode == 0 || in.target_mode == 1, fn, "target_mode must be 0 or 1");
+  RP_REQUIRE(in.B > 0 && in.B < 65536 && in.H > 0 && in.W > 0 && static_cast<long long>(in.H) * in.W < (1LL << 31) &&
+                 (need_iter || num_iters >= 0), fn, "bad size");
+  if (need_iter) RP_REQUIRE(num_iters >= 1, fn, "needs at least one iteration (G_out would stay unwritten)");
+  if (dt && lm_rgbd_check(fn, *dt, in.B)) return 1;
+  RP_REQUIRE(in.workspace_bytes >= rnnpose_lm_workspace_bytes(in.B, in.H, in.W), fn, "workspace too small");
+  return 0;
+}
+
+// every LM entry: the checks, then num_iters iterations from G_in in the form that g_lm_fused and the presence of `info` select
+static int lm_run(const char* fn, const LmInputs& in, const LmDepthTerm* dt, const float* G_in, LmTail tail, bool solve, int num_iters,
+                  bool need_iter, rnnpose_stream_t stream) {
+  if (lm_check(fn, in, dt, G_in, tail, solve, num_iters, need_iter)) return 1;
   hipStream_t st = rp::as_stream(stream);
   for (int it = 0; it < num_iters; ++it) {
-    const float* g = it == 0 ? G_in : G_out;            // later iterations continue in place on the output
-    if (g_lm_fused && info) {
-      launch_lm_step_fused(target, target_mode, weight, depth, depth_eps, K, g, G_out, B, H, W, ep_lambda, lm_lambda, max_update,
-                           workspace, Hm, bv, xi, info, st);
-      continue;
-    }
-    launch_normal_eq(target, target_mode, weight, depth, depth_eps, K, g, B, H, W, workspace, Hm, bv, st);
-    // (g may alias G_out: each thread reads its whole pose before writing it.  A merged finalize + solve kernel was measured
-    //  SLOWER, 26 us vs 7 + 6 us: the solve is a serial fp64 chain that then waits behind the 256-thread reduction's launch)
-    hipLaunchKernelGGL(lm_solve_update_kernel, dim3(rp::cdiv(B, 64)), dim3(64), 0, st, Hm, bv, g, B, ep_lambda,
-                       lm_lambda, max_update, G_out, xi, info);
+    tail.G_in = it == 0 ? G_in : tail.G_out;              // later iterations continue in place on the output
+    launch_lm_iteration(g_lm_fused && tail.info, in, dt, tail, st);
   }
   return rp::check_launch(fn);
+}
+
+int rnnpose_lm_normal_eq_f64(const float* target, int target_mode, const float* weight, const float* depth,
+                             float depth_eps, const float* K, const float* G, int B, int H, int W, void* workspace,
+                             size_t workspace_bytes, double* Hm, double* bv, rnnpose_stream_t stream) {
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
+  return lm_run("rnnpose_lm_normal_eq_f64", in, nullptr, G, lm_tail(workspace, Hm, bv, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, nullptr), false,
+                1, false, stream);
 }
 
 int rnnpose_lm_step_f32(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
                         const float* K, float* G, int B, int H, int W, int num_iters, double ep_lambda, double lm_lambda,
                         double max_update, void* workspace, size_t workspace_bytes, double* Hm, double* bv, float* xi,
                         int* info, rnnpose_stream_t stream) {
-  return lm_step_impl("rnnpose_lm_step_f32", target, target_mode, weight, depth, depth_eps, K, G, G, B, H, W, num_iters,
-                      ep_lambda, lm_lambda, max_update, workspace, workspace_bytes, Hm, bv, xi, info, stream);
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
+  return lm_run("rnnpose_lm_step_f32", in, nullptr, G, lm_tail(workspace, Hm, bv, G, xi, info, ep_lambda, lm_lambda, max_update, nullptr), true,
+                num_iters, false, stream);
 }
 
 int rnnpose_lm_step_io_f32(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
@@ -797,20 +788,9 @@ int rnnpose_lm_step_io_f32(const float* target, int target_mode, const float* we
                            double ep_lambda, double lm_lambda, double max_update, void* workspace, size_t workspace_bytes,
                            double* Hm, double* bv, float* xi, int* info, rnnpose_stream_t stream) {
   RP_REQUIRE(num_iters >= 1, "rnnpose_lm_step_io_f32", "needs at least one iteration (G_out would stay unwritten)");
-  return lm_step_impl("rnnpose_lm_step_io_f32", target, target_mode, weight, depth, depth_eps, K, G_in, G_out, B, H, W,
-                      num_iters, ep_lambda, lm_lambda, max_update, workspace, workspace_bytes, Hm, bv, xi, info, stream);
-}
-
-// the depth arguments shared by the two RGB-D entries
-static int lm_rgbd_check(const char* fn, const float* obs_depth, const int* src_index, const float* theta, const float* K_obs, int B, int S,
-                         int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol) {
-  RP_REQUIRE(obs_depth && theta && K_obs, fn, "null obs_depth / theta / K_obs");
-  RP_REQUIRE(S >= 1 && Ho > 0 && Wo > 0 && static_cast<long long>(Ho) * Wo < (1LL << 31), fn, "bad observed-frame size (S >= 1, Ho, Wo > 0)");
-  RP_REQUIRE(src_index || S == B, fn, "src_index is null: the observed depth must hold one frame per object (S == B)");
-  RP_REQUIRE(std::isfinite(depth_weight) && depth_weight >= 0.f, fn, "depth_weight must be finite and >= 0");
-  RP_REQUIRE(std::isfinite(depth_gate) && depth_gate >= 0.f, fn, "depth_gate must be finite and >= 0");
-  RP_REQUIRE(std::isfinite(edge_tol) && edge_tol >= 0.f, fn, "edge_tol must be finite and >= 0");
-  return 0;
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
+  return lm_run("rnnpose_lm_step_io_f32", in, nullptr, G_in, lm_tail(workspace, Hm, bv, G_out, xi, info, ep_lambda, lm_lambda, max_update, nullptr),
+                true, num_iters, false, stream);
 }
 
 int rnnpose_lm_normal_eq_rgbd_f64(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
@@ -818,16 +798,10 @@ int rnnpose_lm_normal_eq_rgbd_f64(const float* target, int target_mode, const fl
                                   const float* theta, const float* K_obs, int S, int Ho, int Wo, float depth_weight, float depth_gate,
                                   float edge_tol, void* workspace, size_t workspace_bytes, double* Hm, double* bv, double* dstats,
                                   rnnpose_stream_t stream) {
-  const char* fn = "rnnpose_lm_normal_eq_rgbd_f64";
-  RP_REQUIRE(target && weight && depth && K && G && workspace && Hm && bv, fn, "null pointer");
-  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
-  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31), fn, "bad size");
-  if (lm_rgbd_check(fn, obs_depth, src_index, theta, K_obs, B, S, Ho, Wo, depth_weight, depth_gate, edge_tol)) return 1;
-  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
   const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
-  launch_lm_rgbd(false, target, target_mode, weight, depth, depth_eps, K, G, nullptr, B, H, W, dt, 0.0, 0.0, 0.0, workspace, Hm, bv, nullptr,
-                 nullptr, dstats, rp::as_stream(stream));
-  return rp::check_launch(fn);
+  return lm_run("rnnpose_lm_normal_eq_rgbd_f64", in, &dt, G, lm_tail(workspace, Hm, bv, nullptr, nullptr, nullptr, 0.0, 0.0, 0.0, dstats), false,
+                1, false, stream);
 }
 
 int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
@@ -836,19 +810,10 @@ int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const floa
                                 const float* K_obs, int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
                                 void* workspace, size_t workspace_bytes, double* Hm, double* bv, float* xi, int* info, double* dstats,
                                 rnnpose_stream_t stream) {
-  const char* fn = "rnnpose_lm_step_rgbd_io_f32";
-  RP_REQUIRE(target && weight && depth && K && G_in && G_out && workspace && Hm && bv && xi, fn, "null pointer");
-  RP_REQUIRE(target_mode == 0 || target_mode == 1, fn, "target_mode must be 0 or 1");
-  RP_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && static_cast<long long>(H) * W < (1LL << 31), fn, "bad size");
-  RP_REQUIRE(num_iters >= 1, fn, "needs at least one iteration (G_out would stay unwritten)");
-  if (lm_rgbd_check(fn, obs_depth, src_index, theta, K_obs, B, S, Ho, Wo, depth_weight, depth_gate, edge_tol)) return 1;
-  RP_REQUIRE(workspace_bytes >= rnnpose_lm_workspace_bytes(B, H, W), fn, "workspace too small");
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
   const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
-  hipStream_t st = rp::as_stream(stream);
-  for (int it = 0; it < num_iters; ++it)                 // later iterations continue in place on the output, as rnnpose_lm_step_io_f32 does
-    launch_lm_rgbd(g_lm_fused && info, target, target_mode, weight, depth, depth_eps, K, it == 0 ? G_in : G_out, G_out, B, H, W, dt, ep_lambda,
-                   lm_lambda, max_update, workspace, Hm, bv, xi, info, dstats, st);
-  return rp::check_launch(fn);
+  return lm_run("rnnpose_lm_step_rgbd_io_f32", in, &dt, G_in, lm_tail(workspace, Hm, bv, G_out, xi, info, ep_lambda, lm_lambda, max_update, dstats),
+                true, num_iters, true, stream);
 }
 
 int rnnpose_se3_exp_f32(const float* xi, int B, float* out, rnnpose_stream_t stream) {

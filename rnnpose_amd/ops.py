@@ -409,15 +409,36 @@ def _workspace(B, H, W, device, slot=0):
     return ws, n
 
 
-def lm_normal_eq(target, weight, depth, K, G, eps: float = 1e-5):
-    """-> Hm (B,6,6) fp64 (undamped), bv (B,6) fp64             geometry/transformation.py:286-297"""
+def _lm_front(target, weight, depth, K, slot=0):
+    """What the four LM functions do first -> (target, weight, depth, K, B, H, W, target mode, workspace, its bytes)."""
     target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
-    K, G = _chk(K, "intrinsics"), _chk(G, "G")
+    K = _chk(K, "intrinsics")
     B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
     mode = _target_mode(target, H, W)
-    ws, n = _workspace(B, H, W, depth.device)
-    Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
-    bv = torch.empty(B, 6, device=depth.device, dtype=F64)
+    ws, n = _workspace(B, H, W, depth.device, slot)
+    return target, weight, depth, K, B, H, W, mode, ws, n
+
+
+_LM_OUT = dict(G=((4, 4), F32), Hm=((6, 6), F64), bv=((6,), F64), xi=((6,), F32), info=((), torch.int32), dstats=((2,), F64))
+
+
+def _lm_out(out, B, device, names):
+    """The caller's preallocated views, or fresh buffers of the named outputs."""
+    if out is not None:
+        return tuple(out)
+    return tuple(torch.empty(B, *_LM_OUT[k][0], device=device, dtype=_LM_OUT[k][1]) for k in names.split())
+
+
+def _pose_in(G):
+    G = _chk(G, "G").reshape(-1, 4, 4)
+    return G if G.is_contiguous() else G.contiguous()
+
+
+def lm_normal_eq(target, weight, depth, K, G, eps: float = 1e-5):
+    """-> Hm (B,6,6) fp64 (undamped), bv (B,6) fp64             geometry/transformation.py:286-297"""
+    target, weight, depth, K, B, H, W, mode, ws, n = _lm_front(target, weight, depth, K)
+    G = _chk(G, "G")
+    Hm, bv = _lm_out(None, B, depth.device, "Hm bv")
     _launch("rnnpose_lm_normal_eq_f64", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(G), B, H, W,
             _ptr(ws), n, _ptr(Hm), _ptr(bv), _stream(), nbytes=16.0 * B * H * W, work=200.0 * B * H * W)
     return Hm, bv
@@ -440,36 +461,22 @@ def lm_step(target, weight, depth, K, G, num_iters=1, ep_lambda=100.0, lm_lambda
     """num_iters fused GN steps; returns (G_new (B,4,4), Hm, bv, xi, info) of the last iteration.
     out: optional preallocated (G_new, Hm, bv, xi, info) views to write into; slot: workspace slot (see _workspace)."""
     _apply_lm_env()
-    target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
-    K = _chk(K, "intrinsics")
-    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
-    mode = _target_mode(target, H, W)
-    ws, n = _workspace(B, H, W, depth.device, slot)
-    if out is not None and int(num_iters) >= 1:
-        Gd, Hm, bv, xi, info = out          # (every step writes all five outputs for every image)
-        Gin = _chk(G, "G").reshape(-1, 4, 4)
-        if not Gin.is_contiguous():
-            Gin = Gin.contiguous()
-        _launch("rnnpose_lm_step_io_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(Gin), _ptr(Gd), B, H, W,
+    target, weight, depth, K, B, H, W, mode, ws, n = _lm_front(target, weight, depth, K, slot)
+    Gd, Hm, bv, xi, info = _lm_out(out, B, depth.device, "G Hm bv xi info")
+    cost = dict(nbytes=16.0 * B * H * W * int(num_iters), work=200.0 * B * H * W * int(num_iters))
+    if out is not None and int(num_iters) >= 1:         # (every step writes all five outputs for every image)
+        _launch("rnnpose_lm_step_io_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(_pose_in(G)), _ptr(Gd), B, H, W,
                 int(num_iters), float(ep_lambda), float(lm_lambda), float(max_update), _ptr(ws), n, _ptr(Hm), _ptr(bv),
-                _ptr(xi), _ptr(info), _stream(), nbytes=16.0 * B * H * W * int(num_iters), work=200.0 * B * H * W * int(num_iters))
+                _ptr(xi), _ptr(info), _stream(), **cost)
         return Gd, Hm, bv, xi, info
-    if out is not None:
-        Gd, Hm, bv, xi, info = out
-        Gd.copy_(_chk(G, "G").reshape(-1, 4, 4))
-        G = Gd
-        xi.zero_()
-        info.zero_()
-    else:
-        G = _chk(G, "G").reshape(-1, 4, 4).clone()
-        Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
-        bv = torch.empty(B, 6, device=depth.device, dtype=F64)
-        xi = torch.zeros(B, 6, device=depth.device, dtype=F32)
-        info = torch.zeros(B, device=depth.device, dtype=torch.int32)
-    _launch("rnnpose_lm_step_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(G), B, H, W,
+    # in place on a copy of G; without an iteration that copy, a zero xi and a zero info are the result
+    Gd.copy_(_chk(G, "G").reshape(-1, 4, 4))
+    xi.zero_()
+    info.zero_()
+    _launch("rnnpose_lm_step_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(Gd), B, H, W,
             int(num_iters), float(ep_lambda), float(lm_lambda), float(max_update), _ptr(ws), n, _ptr(Hm), _ptr(bv),
-            _ptr(xi), _ptr(info), _stream(), nbytes=16.0 * B * H * W * int(num_iters), work=200.0 * B * H * W * int(num_iters))
-    return G, Hm, bv, xi, info
+            _ptr(xi), _ptr(info), _stream(), **cost)
+    return Gd, Hm, bv, xi, info
 
 
 DEPTH_TERM_DEFAULTS = dict(depth_weight=1.0, depth_gate=0.05, edge_tol=0.02)      # DESIGN.md section 18 (gate and edge tolerance: unmeasured choices)
@@ -528,16 +535,11 @@ def lm_normal_eq_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_
     obs_depth (S,Ho,Wo) or (S,1,Ho,Wo); theta (B,2,3) the crop maps; K_obs (B,3,3) full-frame intrinsics; src_index: an
     ops.SourceIndex, B integers or None (S == B); index_rows (b0, b1): the objects are rows [b0, b1) of src_index.
     -> Hm (B,6,6), bv (B,6), dstats (B,2) fp64 [active pixels, sum v w omega |r3|^2]."""
-    target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
-    K, G = _chk(K, "intrinsics"), _chk(G, "G")
-    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
-    mode = _target_mode(target, H, W)
+    target, weight, depth, K, B, H, W, mode, ws, n = _lm_front(target, weight, depth, K)
+    G = _chk(G, "G")
     obs_depth, theta, K_obs, idx, S, Ho, Wo = _rgbd_args("lm_normal_eq_rgbd", B, obs_depth, theta, K_obs, src_index, index_rows, depth_weight,
                                                          depth_gate, edge_tol)
-    ws, n = _workspace(B, H, W, depth.device)
-    Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
-    bv = torch.empty(B, 6, device=depth.device, dtype=F64)
-    dstats = torch.empty(B, 2, device=depth.device, dtype=F64)
+    Hm, bv, dstats = _lm_out(None, B, depth.device, "Hm bv dstats")
     _launch("rnnpose_lm_normal_eq_rgbd_f64", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(G), B, H, W, _ptr(obs_depth),
             _ptr(idx), _ptr(theta), _ptr(K_obs), S, Ho, Wo, float(depth_weight), float(depth_gate), float(edge_tol), _ptr(ws), n, _ptr(Hm),
             _ptr(bv), _ptr(dstats), _stream(), nbytes=32.0 * B * H * W, work=300.0 * B * H * W)
@@ -552,25 +554,11 @@ def lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_index
     _apply_lm_env()
     if int(num_iters) < 1:
         raise ValueError("lm_step_rgbd: num_iters must be >= 1")
-    target, weight, depth = _chk(target, "target"), _chk(weight, "weight"), _chk(depth, "depth")
-    K = _chk(K, "intrinsics")
-    B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
-    mode = _target_mode(target, H, W)
+    target, weight, depth, K, B, H, W, mode, ws, n = _lm_front(target, weight, depth, K, slot)
     obs_depth, theta, K_obs, idx, S, Ho, Wo = _rgbd_args("lm_step_rgbd", B, obs_depth, theta, K_obs, src_index, index_rows, depth_weight,
                                                          depth_gate, edge_tol)
-    ws, n = _workspace(B, H, W, depth.device, slot)
-    Gin = _chk(G, "G").reshape(-1, 4, 4)
-    if not Gin.is_contiguous():
-        Gin = Gin.contiguous()
-    if out is not None:
-        Gd, Hm, bv, xi, info, dstats = out
-    else:
-        Gd = torch.empty(B, 4, 4, device=depth.device, dtype=F32)
-        Hm = torch.empty(B, 6, 6, device=depth.device, dtype=F64)
-        bv = torch.empty(B, 6, device=depth.device, dtype=F64)
-        xi = torch.empty(B, 6, device=depth.device, dtype=F32)
-        info = torch.empty(B, device=depth.device, dtype=torch.int32)
-        dstats = torch.empty(B, 2, device=depth.device, dtype=F64)
+    Gin = _pose_in(G)
+    Gd, Hm, bv, xi, info, dstats = _lm_out(out, B, depth.device, "G Hm bv xi info dstats")
     _launch("rnnpose_lm_step_rgbd_io_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(Gin), _ptr(Gd), B, H, W,
             int(num_iters), float(ep_lambda), float(lm_lambda), float(max_update), _ptr(obs_depth), _ptr(idx), _ptr(theta), _ptr(K_obs), S, Ho,
             Wo, float(depth_weight), float(depth_gate), float(edge_tol), _ptr(ws), n, _ptr(Hm), _ptr(bv), _ptr(xi), _ptr(info), _ptr(dstats),

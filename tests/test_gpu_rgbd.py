@@ -1,4 +1,4 @@
-"""The depth-aware LM step (csrc/lm.hip: lm_rgbd_eq_kernel; rnnpose_lm_normal_eq_rgbd_f64, rnnpose_lm_step_rgbd_io_f32) against the numpy
+"""The depth-aware LM step (csrc/lm.hip: lm_eq_kernel<DEPTH = true>; rnnpose_lm_normal_eq_rgbd_f64, rnnpose_lm_step_rgbd_io_f32) against the numpy
 restatement tests/rgbd_ref.py in fp32 and fp64, its bit-identity with the plain step when the term is off, the two launch forms, exact
 recovery of a displaced pose, bad arguments, and the refiner end to end (run with -m gpu on an MI355X; everything but the end-to-end and
 dispatcher tests also runs on the host-executed kernels, tests/test_rgbd_on_host.py).

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPECT = {
     "corr_lookup.hip": {"corr_lookup_kernel": (30, 10, 20)},
     "pointwise.hip": {"corr_weight_kernel": (15, 8, 6)},      # (r06: tap pairs -- 3 loads per channel instead of 5)
-    "lm.hip": {"lm_normal_eq_kernel": (16, 12, 10)},       # (the fused-tail instantiation adds its hand-off waits, the finalize loads and the inlined solve: 9; the plain one has 1)
+    "lm.hip": {"lm_eq_kernelILb0E": (16, 12, 10)},         # lm_eq_kernel<DEPTH = false, .>, the plain step (the fused-tail instantiation adds its hand-off waits, the finalize loads and the inlined solve: 9; the plain one has 1)
     "nhwc_ops.hip": {"convex_upsample_nhwc_kernel": (18, 4, 3), "instnorm_apply_kernel": (6, 2, 2), "conv7x7_cin2_kernel": (50, 5, 40)},
     "stem.hip": {"stem_conv7x7_s2_kernel": (20, 4, 1)},        # (r06 persistent form: 2 x 10 patch loads + weights + bias; the next tile's patch is waited for once,
                                                                #  behind the MFMAs; the serialised form has one vmcnt(0) per load)

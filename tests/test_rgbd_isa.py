@@ -1,5 +1,5 @@
 """Compile-time check of the depth-aware LM kernel (CPU only: hipcc cross-compiles gfx950), in the manner of tests/test_isa_guard.py:
-csrc/lm.hip is compiled with the library's flags, and both instantiations of lm_rgbd_eq_kernel (three-launch form, fused tail) must
+csrc/lm.hip is compiled with the library's flags, and both DEPTH = true instantiations of lm_eq_kernel (three-launch form, fused tail) must
 report no spilled VGPR and must issue their loads in batches -- more global loads than full `s_waitcnt vmcnt(0)` waits.  A load under a
 bounds test, or a divergent branch around the tap loads, would bring one full wait per load back (rule 1)."""
 import os
@@ -7,7 +7,7 @@ import re
 
 from test_isa_guard import ROOT, _isa
 
-KERNEL = "lm_rgbd_eq_kernel"
+KERNEL = "lm_eq_kernelILb1E"       # lm_eq_kernel<DEPTH = true, FUSED> in the mangled symbol; ...ILb0E is the plain step of test_isa_guard
 
 
 def test_rgbd_kernel_does_not_spill_and_batches_its_loads(tmp_path):
@@ -27,8 +27,8 @@ def test_rgbd_kernel_does_not_spill_and_batches_its_loads(tmp_path):
         assert loads >= 8 * 3 + 8 * 4, (sym, loads)
         assert loads > w0, f"{sym}: {w0} vmcnt(0) waits for {loads} loads -- the loads are serialised"
         assert counted >= 8, f"{sym}: only {counted} counted waits for {loads} loads"
-    # the kernel the existing guard was written for is a different symbol: the new name does not contain the old one
-    assert not any("lm_normal_eq_kernel" in sym for sym in hits)
+    # the kernels the existing guard was written for are different symbols: its key matches none of these
+    assert not any("lm_eq_kernelILb0E" in sym for sym in hits)
     # the host-execution tier rewrites exactly two full-wait statements of this file (tests/host_exec/build_host.py)
     src = open(os.path.join(ROOT, "rnnpose_amd", "csrc", "lm.hip")).read()
     assert len(re.findall(r'asm volatile\("s_waitcnt vmcnt\(0\)" ::: "memory"\);', src)) == 2

@@ -1,4 +1,4 @@
-"""The depth-aware LM step (csrc/lm.hip: lm_rgbd_eq_kernel and the shared tail / finalize) EXECUTED ON THE HOST (tests/host_exec/, see
+"""The depth-aware LM step (csrc/lm.hip: lm_eq_kernel<DEPTH = true> and the shared tail / finalize) EXECUTED ON THE HOST (tests/host_exec/, see
 tests/test_kernels_on_host.py) in the `-m "not gpu"` tier: the tests of tests/test_gpu_rgbd.py, UNMODIFIED, in a subprocess under the
 plugin tests/host_exec/pytest_hostexec.py.  Left to the GPU: the end-to-end test (it renders and captures graphs) and the dispatcher
 test (the host tensors are CPU tensors)."""
