@@ -45,7 +45,7 @@ class DescriptorEngine:
 
     def _weights(self):
         mods = self._mods()
-        key = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()) for m in mods.values())
+        key = ops.param_key(mods.values())
         if key == self._key:
             return self._w
         P = ops.PackedConv
@@ -70,17 +70,10 @@ class DescriptorEngine:
 
     @staticmethod
     def _conv(pc, src, relu=True, stats=False, in_norm=None):
-        n, h, w, _ = src.shape
         tile = _TILE_128x64 if pc.seg_counts[0] % 32 else _TILE_STRIP160
-        out = torch.empty(n, h, w, pc.c_out, device=src.device, dtype=torch.float32)
-        ts = None
-        if stats:
-            tpi = ops.conv_tiles_per_image(h, w, pc.kh, pc.kw, 1, pc.c_out, tile, n, src_counts=pc.seg_counts, fused_norm=in_norm is not None)
-            ts = torch.empty(n * tpi, pc.c_out, 2, device=src.device, dtype=torch.float64)
         # src_bounded stays False: these layers see raw image values and un-normalised activations (the range check counts)
-        ops.conv2d_nhwc(pc, [(src, 0)], (out, 0), ops.EPI_RELU if relu else ops.EPI_LINEAR, tile_stats=ts, in_norm=in_norm,
-                        tile=tile, src_bounded=False, single_product=False)
-        return out, ts
+        return ops.conv2d_nhwc_new(pc, src, ops.EPI_RELU if relu else ops.EPI_LINEAR, 1, stats, in_norm, tile, src_bounded=False,
+                                   single_product=False)
 
     def _chunk(self, W, img, desc_out, score_out, normalize_output):
         n, _, H, Wd = img.shape

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import env, ops, streams
 
 
 class UpdateEngine:
@@ -28,7 +28,7 @@ class UpdateEngine:
         self._b = None
         self._sets = {}           # (B,h,w,device) -> activation buffer set; kept alive because captured hipGraphs hold raw
         self.epoch = 0            # pointers into them.  Bumped whenever a set is freed: graph caches keyed on it are dropped
-        import os
+        self._ksws = {}           # K-split workspaces (_ksplit_ws)
         # Two half-batch chains on two streams (RNNPOSE_SPLIT_BATCH, default 1 again since r05; 0: ONE full-batch chain on the caller's
         # stream).  Images are independent, so each half of the batch runs its complete inner loop on its own stream: one chain's
         # latency-bound tail kernels and kernel boundaries run under the other chain's convolutions (+2 % on the headline step next to
@@ -39,41 +39,38 @@ class UpdateEngine:
         # that a plain-HIP probe reproduces (tools/probes/pk_f32_vs_mfma.hip), not a visibility problem.  The library is built without
         # packed fp32 since (build.py, tests/test_isa_guard.py) and every schedule is bit-reproducible and bit-identical to the others
         # (tests/test_gpu_reproducibility.py).
-        self.split_batch = os.environ.get("RNNPOSE_SPLIT_BATCH", "1") != "0"
+        self.split_batch = env.flag("RNNPOSE_SPLIT_BATCH", True)
         # flow-feature / flow-head side chain of a lone SMALL chain on a helper stream: off by default since r05 (B = 1, 240 x 240:
         # 4.25 ms per refinement without it, 4.49 with it -- hipGraph replay runs the two-branch graph no faster than the linear one)
-        self.side_stream = os.environ.get("RNNPOSE_SIDE_STREAM", "0") != "0"
-        self.parts = int(os.environ.get("RNNPOSE_PARTS", "2"))
-        self.parts_forced = "RNNPOSE_PARTS" in os.environ                         # explicit part count: no small-batch merging
-        self.fused_mask = os.environ.get("RNNPOSE_FUSED_MASK", "1") != "0"       # mask.2 inside the up-sampling kernel
-        self.resident_1x1 = os.environ.get("RNNPOSE_RESIDENT_1X1", "1") != "0"    # convc1 through csrc/conv1x1_resident.hip
+        self.side_stream = env.flag("RNNPOSE_SIDE_STREAM", False)
+        self.parts = env.number("RNNPOSE_PARTS", 2)
+        self.parts_forced = env.text("RNNPOSE_PARTS") is not None                      # explicit part count: no small-batch merging
+        self.fused_mask = env.flag("RNNPOSE_FUSED_MASK", True)       # mask.2 inside the up-sampling kernel
+        self.resident_1x1 = env.flag("RNNPOSE_RESIDENT_1X1", True)    # convc1 through csrc/conv1x1_resident.hip
         # r06: window lookup + convc1 as ONE launch (csrc/corr_convc1.hip: the 324-channel corr tensor is never written).  Built, parity-
         # tested and NOT faster: alone 39.8 us against 23.1 + 18.7 us for the two kernels at B = 4 (67 vs 70 at B = 8), on the step 754 vs 756
         # iters/s (profiles/r06_lookup_convc1_fusion.txt) -- the lookup is bound by the sectors its gather touches (81 MB per launch), and a
         # one-round launch runs its footprint phases and its MFMA phases in lock step, so the fusion saves the 25-MB round trip of the
         # tensor and nothing else.  OFF by default; RNNPOSE_FUSED_LOOKUP=1 switches it on.
-        self.fused_lookup = os.environ.get("RNNPOSE_FUSED_LOOKUP", "0") != "0"
+        self.fused_lookup = env.flag("RNNPOSE_FUSED_LOOKUP", False)
         # r06: RNNPOSE_FUSED_INDUCED=1 forms the pose-induced coordinates inside their first consumers (window lookup, flow-feature convolution:
         # ops.InducedCoords) instead of by a 5-us launch of their own in front of every iteration -- bit-identical values (csrc/induced.cuh), one
         # launch fewer per iteration, and measured EQUAL on the step (750.6 vs 749.5 iters/s, S1 4.08 vs 4.08 ms: what the launch cost, the two
         # consumers now spend on 4 depth taps per pixel and level / per patch entry; profiles/r06_fused_induced.txt): an option, off by default
-        self.fused_induced = os.environ.get("RNNPOSE_FUSED_INDUCED", "0") != "0"
-        self.ksplit = os.environ.get("RNNPOSE_KSPLIT", "1") != "0"                # small launches (B = 1 crops) split their K loop
+        self.fused_induced = env.flag("RNNPOSE_FUSED_INDUCED", False)
+        self.ksplit = env.flag("RNNPOSE_KSPLIT", True)                # small launches (B = 1 crops) split their K loop
         # SPLIT TENSORS (include/rnnpose_hip.h): every activation that only feeds further convolutions is written once, by its
         # producer's epilogue, as fp16 hi|lo pairs and staged by the consumers with a plain 16-byte copy (no per-tile re-split).
         # r03 (128-row kernels, which re-stage through registers anyway): -1.3 % on the step, off.  r04: the strip kernels take split
         # tensors by LDS-DMA (no registers, no split instructions in the loop) and their specialised epilogue writes the split form
         # at 4-6 us per workgroup: +2-3 % on the step (profiles/r04_ab_split_tensors.txt, same box: 724 vs 690-713 iters/s).  ON by
         # default; RNNPOSE_SPLIT_TENSORS=0 restores fp32 activations everywhere (tests cover both).
-        self.hl = os.environ.get("RNNPOSE_SPLIT_TENSORS", "1") != "0"
+        self.hl = env.flag("RNNPOSE_SPLIT_TENSORS", True)
         # cfg.raft.mixed_precision: one fp16 product per multiply-add in the 160-row strip kernels.  Carried by the ENGINE its PoseRefiner
         # configures (r04 used a process-wide default that direct callers of ops / cf_net inherited from the last refiner: ADVICE r04)
         self.single_product = False
         # tile-shape override per layer for measurements: RNNPOSE_CONV_TILE="zr=3,q=1,heads=2" (0 auto, see conv2d_nhwc)
-        self.tile = {}
-        for kv in filter(None, os.environ.get("RNNPOSE_CONV_TILE", "").split(",")):
-            k, v = kv.split("=")
-            self.tile[k] = int(v)
+        self.tile = {k: int(v) for k, v in (kv.split("=") for kv in filter(None, env.text("RNNPOSE_CONV_TILE", "").split(",")))}
 
     # ---- weights ---------------------------------------------------------------------------------------------
     def _params(self):
@@ -84,7 +81,7 @@ class UpdateEngine:
 
     def param_key(self):
         """Identity of the live parameters: changes on load_state_dict / in-place updates / .to()."""
-        return tuple((m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()) for m in self._params())
+        return ops.param_key(self._params())
 
     def refresh(self):
         """Re-pack the fp16 hi/lo weights if the module's parameters changed; -> the key captured graphs depend on."""
@@ -103,8 +100,7 @@ class UpdateEngine:
         P = ops.PackedConv
         w = dict(
             convc1=P(e.convc1.weight, e.convc1.bias, [e.convc1.weight.shape[1]]),
-            convc1r=(ops.PackedConv1x1(e.convc1.weight, e.convc1.bias)
-                     if (e.convc1.weight.shape[0] == 256 and e.convc1.weight.shape[1] <= 352 and e.convc1.weight.shape[1] % 4 == 0) else None),
+            convc1r=ops.PackedConv1x1(e.convc1.weight, e.convc1.bias) if ops.PackedConv1x1.fits(e.convc1.weight) else None,
             convc2=P(e.convc2.weight, e.convc2.bias, [256]),
             convf1_wt=e.convf1.weight.detach().float().reshape(e.convf1.weight.shape[0], 98).t().contiguous(),   # (98, 128)
             convf1_b=e.convf1.bias.detach().float().contiguous(),
@@ -159,36 +155,15 @@ class UpdateEngine:
     def _ksplit_ws(self, b0, b1, which):
         """K-split workspace (ops.conv_ksplit_workspace) of the chain of images [b0, b1) -- `which` 0: its main stream, 1: its
         helper stream (launches that can run concurrently must not share one).  None when the chain has too many pixels for
-        any of its convolutions to split (the library splits launches of <= 96 tiles).  Allocated on first use, i.e. in the
-        eager warm-up runs before a hipGraph capture."""
-        B, h, w, dev = self._buf_key
-        if not self.ksplit or (b1 - b0) * h * w > 96 * 128:
-            return None
-        reg = self.__dict__.setdefault("_ksws", {})
-        key = (self._buf_key, self.epoch, b0, which)
-        ws = reg.get(key)
-        if ws is None:
-            for k in [k for k in reg if k[1] != self.epoch]:
-                del reg[k]
-            ws = reg[key] = ops.conv_ksplit_workspace(self._b["hA"].device)
-        return ws
+        any of its convolutions to split.  Workspaces of buffer sets that were freed since (other epochs) are dropped."""
+        _, h, w, _ = self._buf_key
+        return ops.ksplit_workspace_in(self._ksws, (self._buf_key, self.epoch, b0, which), self.ksplit, (b1 - b0) * h * w,
+                                       self._b["hA"].device, keep=lambda k: k[1] == self.epoch)
 
     def select(self, buf_key):
         """Make the buffer set a captured graph was recorded on the current one (graph replay path)."""
         (B, h, w, dev), _ = buf_key
         return self._buffers(B, h, w, dev)
-
-    def _stream(self, device, i):
-        """Helper stream i (0, 1: the two batch halves; 2: the flow-feature / flow-head side chain of an unsplit step) --
-        from the per-device set that is bound to distinct hardware queues (rnnpose_amd/streams.py)."""
-        from .streams import reserve
-        if ops.profiling():
-            # per-launch timing (ops.profile): everything on the caller's stream, so that each launch is timed ALONE on the
-            # chip -- the duration a roofline wants (and what rocprofv3's kernel trace, which serialises kernels, reports).
-            # Timed next to its twin on the other stream, a launch's duration includes the sharing.
-            return torch.cuda.current_stream()
-        ss = reserve(device)
-        return (ss.chain + [ss.aux] + ss.extra)[i]
 
     def load_state(self, net, inp):
         """net, inp: (B,128,h,w) NCHW (tanh / relu of the context features, model/CFNet.py:131-133)."""
@@ -230,7 +205,7 @@ class UpdateEngine:
         ops.nchw_to_nhwc(corr, b["corr"])
         self._hoist_inp(W, b)
         flow = flow.float().contiguous()
-        self._chain(W, b, flow, torch.cuda.current_stream(), None, flow_is_delta=True, want_mask=True)
+        streams.drain(self._chain_gen(W, b, flow, torch.cuda.current_stream(), None, flow_is_delta=True, want_mask=True))
         return (ops.nhwc_to_nchw(b["hA"]), ops.nhwc_to_nchw(b["mask"]), ops.nhwc_to_nchw(b["delta"]))
 
     MIN_CHAIN_PIXELS = 8192     # 1/8-resolution pixels per chain below which the batch stays ONE chain
@@ -273,39 +248,13 @@ class UpdateEngine:
         # helper stream for the flow-feature / flow-head side chain: opt-in (RNNPOSE_SIDE_STREAM=1), and only for a lone SMALL chain; it
         # measured equal at the headline (695-699 iters/s either way) and slower at B = 1 (see __init__)
         small = coords1_part.shape[0] * coords1_part.shape[2] * coords1_part.shape[3] < self.MIN_CHAIN_PIXELS
-        yield from self._chain_gen(W, view, coords1_part, st, self._stream(coords1_part.device, 2) if (single and small and self.side_stream) else None,
+        yield from self._chain_gen(W, view, coords1_part, st, streams.helper_stream(coords1_part.device, 2) if (single and small and self.side_stream) else None,
                                    have_cor1=fused, induced=induced)
         if self.fused_mask:         # mask.2 + up-sampling in one kernel (the chain skipped its mask.2 launch)
             ops.mask_upsample(W["mask2u"], view["heads"], 256, view["flow_lr"], out=flow_up_part)
         else:
             ops.convex_upsample_nhwc(view["flow_lr"], view["mask"], out=flow_up_part)
         yield
-
-    @staticmethod
-    def run_interleaved(jobs, main):
-        """jobs: [(generator, stream)].  Every generator's launches go to its stream; the generators are advanced in turn.
-        Streams other than `main` start after everything already on `main` and `main` waits for them at the end: ONE fork
-        and ONE join, however long the generators are -- a cross-queue dependency costs ~100 us on this GPU (r02 timeline:
-        the second chain of every inner iteration started 115 us after the event it waited for), an in-queue one ~1 us."""
-        fork = torch.cuda.Event()
-        fork.record(main)
-        for _, st in jobs:
-            if st is not main:
-                st.wait_event(fork)
-        active = list(jobs)
-        while active:
-            for item in list(active):
-                g, st = item
-                with torch.cuda.stream(st):
-                    try:
-                        next(g)
-                    except StopIteration:
-                        active.remove(item)
-        for _, st in jobs:
-            if st is not main:
-                j = torch.cuda.Event()
-                j.record(st)
-                main.wait_event(j)
 
     def step(self, corr_fn, coords1, tail=None, flow_up=None):
         """coords1 (B,2,h,w) -> (coords1 + delta_flow (B,2,h,w), flow_up (B,2,8h,8w)).
@@ -326,14 +275,10 @@ class UpdateEngine:
 
         jobs = []
         for i, (b0, b1) in enumerate(hv):
-            st = main if i == 0 else self._stream(coords1.device, i)
+            st = main if i == 0 else streams.helper_stream(coords1.device, i)
             jobs.append((half(b0, b1, st), st))
-        self.run_interleaved(jobs, main)
+        streams.run_interleaved(jobs, main)
         return self._b["coords1"], flow_up
-
-    def _chain(self, W, b, coords1, main, side, flow_is_delta=False, want_mask=False):
-        for _ in self._chain_gen(W, b, coords1, main, side, flow_is_delta, want_mask):
-            pass
 
     def _chain_gen(self, W, b, coords1, main, side, flow_is_delta=False, want_mask=False, have_cor1=False, induced=None):
         """The update block on the (sub-)batch views `b`, issued on stream `main` (current) with `side` as helper; yields
@@ -373,14 +318,7 @@ class UpdateEngine:
         if side is None:
             yield from flow_chain()
         else:
-            fork = torch.cuda.Event()
-            fork.record(main)
-            side.wait_event(fork)
-            with torch.cuda.stream(side):
-                for _ in flow_chain():
-                    pass
-                join = torch.cuda.Event()
-                join.record(side)
+            join = streams.side_branch(main, side, lambda: streams.drain(flow_chain()))
         if have_cor1:                                                               # (r06: convc1 ran inside the lookup launch)
             pass
         elif self.resident_1x1 and W["convc1r"] is not None:
@@ -419,13 +357,7 @@ class UpdateEngine:
                 ops.conv2d_nhwc(W["mask2"], [(b["heads"], 256)], (b["mask"], 0), ops.EPI_LINEAR, single_product=self.single_product)  # 0.25 * mask.2(relu(mask.0(h)))
                 yield
             return
-        fork2 = torch.cuda.Event()
-        fork2.record(main)
-        side.wait_event(fork2)
-        with torch.cuda.stream(side):
-            head()
-            join2 = torch.cuda.Event()
-            join2.record(side)
+        join2 = streams.side_branch(main, side, head)
         if mask_here:
             ops.conv2d_nhwc(W["mask2"], [(b["heads"], 256)], (b["mask"], 0), ops.EPI_LINEAR, single_product=self.single_product)      # 0.25 * mask.2(relu(mask.0(h)))
         main.wait_event(join2)
@@ -439,16 +371,15 @@ class EncoderEngine:
     one fused HIP pass each; the stride-2 3x3 / 1x1 convolutions use the kernel's strided mode.  No MIOpen, no ATen math."""
 
     def __init__(self, fnet):
-        import os
         self.fnet = fnet
         self._key = None
         self._w = None
-        self._side = None
-        self.resident_1x1 = os.environ.get("RNNPOSE_RESIDENT_1X1", "1") != "0"
-        self.ksplit = os.environ.get("RNNPOSE_KSPLIT", "1") != "0"
+        self._ksws = {}
+        self.resident_1x1 = env.flag("RNNPOSE_RESIDENT_1X1", True)
+        self.ksplit = env.flag("RNNPOSE_KSPLIT", True)
         self.single_product = False                   # cfg.raft.mixed_precision, set by the PoseRefiner that owns the encoder (see UpdateEngine)
-        self.split_batch = os.environ.get("RNNPOSE_SPLIT_ENCODER", "1") != "0"
-        self.parts = int(os.environ.get("RNNPOSE_ENCODER_PARTS", "1"))
+        self.split_batch = env.flag("RNNPOSE_SPLIT_ENCODER", True)
+        self.parts = env.number("RNNPOSE_ENCODER_PARTS", 1)
         # one stream per image set (rendered | observed) -- the r02-r03 schedule, the default again since r05 for image sets that fill
         # the chip: one set's HBM-bound normalisation passes and latency-bound finalize launches run under the other set's convolutions
         # (+1-2 % on the headline step, +2 % at B = 16 240 x 240).  Small sets run as ONE concatenated batch on one stream: the fork / join
@@ -456,8 +387,7 @@ class EncoderEngine:
         # B = 2 480 x 640: equal; profiles/r05_ab_encoder_streams_small.txt).  r04 had merged ALL sets because runs with two active
         # streams were not bit-reproducible; r05 found and removed the cause (UpdateEngine.__init__).
         # RNNPOSE_ENCODER_MERGE=1 / 0: always one batch / always one stream per set.
-        m = os.environ.get("RNNPOSE_ENCODER_MERGE")
-        self.merge_sets = None if m is None else (m != "0")
+        self.merge_sets = env.flag("RNNPOSE_ENCODER_MERGE", None)
 
     MIN_SET_PIXELS = 800_000      # full-resolution pixels per image set from which the sets get their own streams
 
@@ -480,33 +410,23 @@ class EncoderEngine:
     def _weights(self):
         convs = self._mine()
         convs["stem"] = self.fnet.conv1
-        key = tuple((m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()) for m in convs.values())
+        key = ops.param_key(convs.values())
         if key != self._key:
             stem = convs.pop("stem")
             self._w = {k: ops.PackedConv(m.weight, m.bias, [m.weight.shape[1]]) for k, m in convs.items()}
             self._w["stem"] = ops.PackedStem(stem.weight, stem.bias)
             oc = convs["out"]           # the 1x1 output convolution (extractor.py:155: 128 -> 256) in the LDS-resident 1x1 kernel
-            ok = tuple(oc.weight.shape[2:]) == (1, 1) and oc.weight.shape[0] == 256 and oc.weight.shape[1] <= 352 and oc.weight.shape[1] % 4 == 0
-            self._w["outr"] = ops.PackedConv1x1(oc.weight, oc.bias) if ok else None
+            self._w["outr"] = ops.PackedConv1x1(oc.weight, oc.bias) if ops.PackedConv1x1.fits(oc.weight) else None
             self._key = key
         return self._w
 
     @staticmethod
     def _conv(pc, x, stride=1, stats=True, in_norm=None, ks=None, sp=False):
-        """-> (out, tile_stats or None): the convolution's epilogue also emits the per-tile column statistics the following
-        instance norm needs (saves re-reading the tensor once; output rows are tiled per image for that).
-        in_norm: mean / rstd of `x`, which is then a RAW convolution output normalised (+ ReLU) in this convolution's load."""
-        B, H, W, _ = x.shape
-        Ho, Wo = -(-H // stride), -(-W // stride)
-        out = torch.empty(B, Ho, Wo, pc.c_out, device=x.device, dtype=torch.float32)
-        ts = torch.empty(B * ops.conv_tiles_per_image(H, W, pc.kh, pc.kw, stride, pc.c_out, 0, B, src_counts=pc.seg_counts, fused_norm=in_norm is not None),
-                         pc.c_out, 2, device=x.device, dtype=torch.float64) if stats else None
-        # src_bounded: every convolution input of the encoder is an instance-normalised map (|.| <= sqrt(H*W)) or a ReLU sum of a
-        # few of them (extractor.py:48-58): two orders of magnitude inside the fp16x3 range, so the in-loop range check is skipped
-        # (the stem, which sees the raw image, and the update block keep theirs)
-        ops.conv2d_nhwc(pc, [(x, 0)], (out, 0), ops.EPI_LINEAR, stride=stride, tile_stats=ts, in_norm=in_norm, src_bounded=True,
-                        ksplit_ws=ks, single_product=sp)
-        return out, ts
+        """-> (out, tile_stats or None) of ops.conv2d_nhwc_new.
+        src_bounded: every convolution input of the encoder is an instance-normalised map (|.| <= sqrt(H*W)) or a ReLU sum of a
+        few of them (extractor.py:48-58): two orders of magnitude inside the fp16x3 range, so the in-loop range check is skipped
+        (the stem, which sees the raw image, and the update block keep theirs)."""
+        return ops.conv2d_nhwc_new(pc, x, ops.EPI_LINEAR, stride, stats, in_norm, src_bounded=True, ksplit_ws=ks, single_product=sp)
 
     @staticmethod
     def _block_gen(W, name, blk, x, x_norm=None, ks=None, sp=False):
@@ -534,15 +454,6 @@ class EncoderEngine:
                                       residual_relu=bool(res_norm and res_norm[1]))               # relu(x + relu(IN(.)))
         yield
         return out
-
-    @staticmethod
-    def _block(W, name, blk, x):
-        g = EncoderEngine._block_gen(W, name, blk, x)
-        try:
-            while True:
-                next(g)
-        except StopIteration as e:
-            return e.value
 
     @torch.no_grad()
     def __call__(self, images, normalize=True, split_out=False):
@@ -573,63 +484,26 @@ class EncoderEngine:
         # (r03: small image sets -- 2 x 1 x 240 x 240 -- as ONE concatenated batch instead of two streams measured 1.5 % slower:
         #  5.16 vs 5.08 ms per refinement; the two launch chains do overlap in graph replay)
         if len(imgs) > 1:                      # one stream per input tensor (rendered | observed)
-            jobs, o = [], 0
-            for t in imgs:
-                jobs.append((t, o, o + t.shape[0]))
-                o += t.shape[0]
+            cuts = [sum(t.shape[0] for t in imgs[:i]) for i in range(len(imgs) + 1)]
+            jobs = [(t, a, b) for t, a, b in zip(imgs, cuts[:-1], cuts[1:])]
         else:
             parts = max(1, min(self.parts if self.split_batch else 1, N))
             cuts = [N * i // parts for i in range(parts + 1)]
             jobs = [(imgs[0][a:b], a, b) for a, b in zip(cuts[:-1], cuts[1:])]
         main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        joins = []
 
-        def job(x_part, b0, b1, st, ji):
-            if st is not main:
-                st.wait_event(fork)
+        def job(x_part, b0, b1, ji):
             yield from self._forward_gen(W, x_part, out[b0:b1], normalize, split_out, ks=self._ksplit_ws(ji, x_part))
-            if st is not main:
-                j = torch.cuda.Event()
-                j.record(st)
-                joins.append(j)
 
-        # launches of the jobs are issued alternately (see UpdateEngine.step: hipGraphLaunch submits in capture order)
-        active = []
-        for hi_, (x_part, b0, b1) in enumerate(jobs):
-            st = main if hi_ == 0 else self._second_stream(dev, hi_)
-            active.append((job(x_part, b0, b1, st, hi_), st))
-        while active:
-            for item in list(active):
-                g, st = item
-                with torch.cuda.stream(st):
-                    try:
-                        next(g)
-                    except StopIteration:
-                        active.remove(item)
-        for j in joins:
-            main.wait_event(j)
+        # launches of the jobs are issued alternately; job 0 on the caller's stream, job i >= 1 on helper stream (i - 1) % 3
+        streams.run_interleaved([(job(x_part, b0, b1, i), main if i == 0 else streams.helper_stream(dev, (i - 1) % 3))
+                                 for i, (x_part, b0, b1) in enumerate(jobs)], main)
         return ops.SplitTensor(out, ops.A_SCALE) if split_out else out
 
     def _ksplit_ws(self, ji, x_part):
         """K-split workspace of job (stream) ji, or None when even the 1/8-resolution layers have too many tiles to split."""
         n, _, H, Wd = x_part.shape
-        if not self.ksplit or n * ((H + 7) // 8) * ((Wd + 7) // 8) > 96 * 128:
-            return None
-        reg = self.__dict__.setdefault("_ksws", {})
-        key = (ji, str(x_part.device))
-        if key not in reg:
-            reg[key] = ops.conv_ksplit_workspace(x_part.device)
-        return reg[key]
-
-    def _second_stream(self, device, i):
-        """Stream of image set / batch part i >= 1 (rnnpose_amd/streams.py: distinct hardware queues)."""
-        from .streams import reserve
-        if ops.profiling():          # per-launch timing: one stream, every launch alone on the chip (UpdateEngine._stream)
-            return torch.cuda.current_stream()
-        ss = reserve(device)
-        return (ss.chain + [ss.aux])[(i - 1) % 3]
+        return ops.ksplit_workspace_in(self._ksws, (ji, str(x_part.device)), self.ksplit, n * ((H + 7) // 8) * ((Wd + 7) // 8), x_part.device)
 
     def _forward_gen(self, W, x_nchw, out, normalize, split_out=False, ks=None):
         """One image set through the encoder (extractor.py:187-232); yields after every launch group."""

@@ -26,7 +26,7 @@ class ResidualBlock(nn.Module):
 
     def forward(self, x):
         """(B,C,H,W) NCHW -> NCHW (extractor.py:48-58) through the NHWC kernels of the encoder engine."""
-        from . import ops
+        from . import ops, streams
         from .engine import EncoderEngine
         if not x.is_cuda:
             raise RuntimeError("ResidualBlock runs on the GPU only (no CPU path in rnnpose_amd)")
@@ -34,7 +34,7 @@ class ResidualBlock(nn.Module):
         W = {"b.c1": pc(self.conv1), "b.c2": pc(self.conv2)}
         if self.downsample is not None:
             W["b.down"] = pc(self.downsample[0])
-        y = EncoderEngine._block(W, "b", self, ops.nchw_to_nhwc(x))
+        y = streams.drain(EncoderEngine._block_gen(W, "b", self, ops.nchw_to_nhwc(x)))
         return ops.nhwc_to_nchw(y)
 
 

@@ -11,7 +11,7 @@ from contextlib import contextmanager
 
 import torch
 
-from . import _lib
+from . import _lib, env
 
 F32 = torch.float32
 F64 = torch.float64
@@ -574,9 +574,9 @@ def _apply_lm_env():
     global _lm_fused_env_applied
     if not _lm_fused_env_applied:
         _lm_fused_env_applied = True
-        v = _os.environ.get("RNNPOSE_LM_FUSED")
+        v = env.flag("RNNPOSE_LM_FUSED", None)
         if v is not None:
-            _lib.call("rnnpose_lm_fused_tail", int(v != "0"))
+            _lib.call("rnnpose_lm_fused_tail", int(v))
 
 
 def lm_fused_tail(enable: bool = True):
@@ -671,6 +671,12 @@ class PackedConv:
         self.bias = b.contiguous()
         _lib.call("rnnpose_conv_pack_weights_f16x3", _ptr(w), self.c_out, self.c_in, self.kh, self.kw, segs,
                   len(self.seg_counts), self.w_scale, _ptr(self.w_packed), _stream())
+
+
+def param_key(modules):
+    """Identity of the live parameters of `modules` (each with .weight and .bias): changes on load_state_dict / in-place updates / .to().
+    The packed copies the engines cache, and every captured graph, depend on it."""
+    return tuple((m.weight._version, m.weight.data_ptr(), m.bias._version, m.bias.data_ptr()) for m in modules)
 
 
 def _nhwc(t, name):
@@ -800,22 +806,16 @@ def _apply_conv_env():
     global _conv_env_applied
     if not _conv_env_applied:
         _conv_env_applied = True
-        v = _os.environ.get("RNNPOSE_SPATIAL_TILES")
-        if v is not None:
-            _lib.call("rnnpose_conv_spatial_tiles", int(v != "0"))
-        v = _os.environ.get("RNNPOSE_KSPLIT")
-        if v is not None:
-            _lib.call("rnnpose_conv_ksplit", int(v != "0"))
-        v = _os.environ.get("RNNPOSE_LOOKUP_VARIANT")      # 0: the r01-r05 window-lookup kernel (same-box A/B; bit-identical results)
-        if v is not None:
-            _lib.call("rnnpose_corr_lookup_variant", int(v != "0"))
-        v = _os.environ.get("RNNPOSE_STRIP")               # 0: the automatic tile choice never takes the strip kernels (same-box A/B);
-        if v is not None:                                  # 2 / 3: strips with one / two column tiles per wave only
-            _lib.call("rnnpose_conv_strip", int(v))
-        v = _os.environ.get("RNNPOSE_CORR_VARIANT")           # 0 / 1: volume kernel with register-staged / LDS-DMA operands (same-box A/B)
-        if v is not None:
-            _lib.call("rnnpose_corr_variant", int(v))
-        v = _os.environ.get("RNNPOSE_KSPLIT_LIMITS")          # "max_tiles,max_splits" (measurement)
+        # same-box A/B switches (what each does: env.py); unset: nothing is called, the library's own default stays
+        for name, entry, read in (("RNNPOSE_SPATIAL_TILES", "rnnpose_conv_spatial_tiles", env.flag),
+                                  ("RNNPOSE_KSPLIT", "rnnpose_conv_ksplit", env.flag),
+                                  ("RNNPOSE_LOOKUP_VARIANT", "rnnpose_corr_lookup_variant", env.flag),
+                                  ("RNNPOSE_STRIP", "rnnpose_conv_strip", env.number),
+                                  ("RNNPOSE_CORR_VARIANT", "rnnpose_corr_variant", env.number)):
+            v = read(name, None)
+            if v is not None:
+                _lib.call(entry, int(v))
+        v = env.text("RNNPOSE_KSPLIT_LIMITS")                 # "max_tiles,max_splits" (measurement)
         if v:
             a, b = (int(t) for t in v.split(","))
             _lib.call("rnnpose_conv_ksplit_limits", a, b)
@@ -844,6 +844,36 @@ def conv_ksplit_workspace(device):
     """Zeroed workspace for conv2d_nhwc(ksplit_ws=...): one per chain of launches that can run concurrently with another."""
     n = int(_lib.load().rnnpose_conv_ksplit_workspace_bytes())
     return torch.zeros((n + 3) // 4, device=device, dtype=torch.int32)
+
+
+KSPLIT_MAX_PIXELS = 96 * 128      # the library splits launches of at most 96 tiles (rnnpose_conv_ksplit_limits) of 128 output pixels
+
+
+def ksplit_workspace_in(reg, key, enabled, pixels, device, keep=None):
+    """The engines' registry of K-split workspaces: -> reg[key], allocated on first use (i.e. in the eager warm-up runs before a hipGraph
+    capture), or None: K-split off, or none of the chain's launches can split (more than KSPLIT_MAX_PIXELS output pixels in its smallest).
+    keep(k): which other entries survive a new allocation."""
+    if not enabled or pixels > KSPLIT_MAX_PIXELS:
+        return None
+    if key not in reg:
+        for k in [k for k in reg if keep is not None and not keep(k)]:
+            del reg[k]
+        reg[key] = conv_ksplit_workspace(device)
+    return reg[key]
+
+
+def conv2d_nhwc_new(pc: PackedConv, x, epilogue: int = EPI_LINEAR, stride: int = 1, stats: bool = False, in_norm=None, tile: int = 0, **kw):
+    """conv2d_nhwc of the one source x (B,H,W,C) into a fresh tensor -> (out, tile_stats or None).  stats: the epilogue also emits the per-tile
+    column statistics the following instance norm needs (saves re-reading the tensor once; output rows are tiled per image for that), sized for
+    the kernel this launch takes.  in_norm: mean / rstd of `x`, then a RAW convolution output normalised (+ ReLU) in this convolution's load."""
+    B, H, W, _ = x.shape
+    out = torch.empty(B, -(-H // stride), -(-W // stride), pc.c_out, device=x.device, dtype=F32)
+    ts = None
+    if stats:
+        tpi = conv_tiles_per_image(H, W, pc.kh, pc.kw, stride, pc.c_out, tile, B, src_counts=pc.seg_counts, fused_norm=in_norm is not None)
+        ts = torch.empty(B * tpi, pc.c_out, 2, device=x.device, dtype=F64)
+    conv2d_nhwc(pc, [(x, 0)], (out, 0), epilogue, stride=stride, tile_stats=ts, in_norm=in_norm, tile=tile, **kw)
+    return out, ts
 
 
 _nchw_pc = {}
@@ -1025,11 +1055,17 @@ def convex_upsample_nhwc(flow_lr, mask, out=None):
 class PackedConv1x1:
     """Weights of a 1x1 convolution with 256 outputs and <= 352 inputs for the LDS-resident kernel (csrc/conv1x1_resident.hip)."""
 
+    @staticmethod
+    def fits(weight) -> bool:
+        """Can the LDS-resident kernel run this layer: a (256, c_in <= 352, 1, 1) weight with c_in % 4 == 0."""
+        s = tuple(weight.shape)
+        return len(s) == 4 and s[0] == 256 and s[2:] == (1, 1) and s[1] % 4 == 0 and s[1] <= 352
+
     def __init__(self, weight, bias, a_scale: float = A_SCALE):
         import math
         range_guard_arm(weight.device)
         w = _chk(weight.detach(), "weight")
-        if w.dim() != 4 or w.shape[0] != 256 or w.shape[2:] != (1, 1) or w.shape[1] % 4 or w.shape[1] > 352:
+        if not self.fits(w):
             raise ValueError("needs a (256, c_in <= 352, 1, 1) weight with c_in % 4 == 0")
         self.c_in = int(w.shape[1])
         wmax = float(w.abs().max())
@@ -1109,8 +1145,7 @@ def mask_upsample(pm: PackedMaskHead, x, x_c_offset, flow_lr, out=None):
 # device counter; PoseRefiner.forward returns the counter as a device tensor ("f16x3_range_events"), so a silent clamp --
 # something the fp32 reference cannot do -- is visible in the public output without a host synchronisation.
 # RNNPOSE_RANGE_GUARD=0 switches it off (measurement only).
-import os as _os
-_guard_env = _os.environ.get("RNNPOSE_RANGE_GUARD", "1") != "0"
+_guard_env = env.flag("RNNPOSE_RANGE_GUARD", True)
 _guard_on = False
 _guard_devices = set()
 

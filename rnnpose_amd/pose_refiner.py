@@ -19,12 +19,10 @@ What is different, on purpose (DESIGN.md section "Batched semantics"):
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import env, ops, streams
 from .cfnet import AttrDict, GRU_CFUpdator, ImageFeaEncoder
 from .corr import coords_grid as coords_grid_lowres
 from .transformation import EP_LMBDA, LM_LMBDA, SE3Sequence, coords_grid
@@ -128,8 +126,8 @@ class PoseRefiner(nn.Module):
         # hipGraph replay of the inner-iteration body (~25 launches): at the reference's own working size (B=1,
         # 240x240) the loop is launch-bound, not GPU-bound.  Falls back to eager launches if capture is refused.
         self.use_graph = use_graph
-        self.split_fmaps = os.environ.get("RNNPOSE_SPLIT_FMAPS", "1") != "0"
-        self.mixed_precision = bool(cfg.get("raft", {}).get("mixed_precision", False)) or os.environ.get("RNNPOSE_MIXED_PRECISION", "0") != "0"
+        self.split_fmaps = env.flag("RNNPOSE_SPLIT_FMAPS", True)
+        self.mixed_precision = bool(cfg.get("raft", {}).get("mixed_precision", False)) or env.flag("RNNPOSE_MIXED_PRECISION", False)
         if self.mixed_precision:
             # the reference's YAMLs set raft.mixed_precision: True (config/linemod/template_fw0.5.yml:88): loading one changes the arithmetic
             import warnings
@@ -144,7 +142,6 @@ class PoseRefiner(nn.Module):
         self._shapes = {}
         self._outer_graphs = {}
         self._outer_captures = 0
-        self.loop_timing = None           # set to [] to collect HIP events around the per-half graph replays
         self._wkey = None                 # identity of the live parameters + engine buffers every captured graph depends on
         self._clear()
 
@@ -225,12 +222,7 @@ class PoseRefiner(nn.Module):
                 return self._outer_body(views)
             self._outer_captures += 1
             try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._outer_body(views)
-                torch.cuda.current_stream().wait_stream(side)
+                streams.warm_up(lambda: [self._outer_body(views) for _ in range(2)])
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     out = self._outer_body(views)
@@ -323,9 +315,9 @@ class PoseRefiner(nn.Module):
         main = torch.cuda.current_stream()
         jobs = []
         for k, (b0, b1) in enumerate(hv):
-            st = main if k == 0 else eng._stream(dev, k)
+            st = main if k == 0 else streams.helper_stream(dev, k)
             jobs.append((self._half_loop(bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd), st))
-        eng.run_interleaved(jobs, main)
+        streams.run_interleaved(jobs, main)
         if rgbd is not None:
             rgbd["stats"] = bufs["dstats"]
         return bufs["big"], bufs["small"]
@@ -370,27 +362,12 @@ class PoseRefiner(nn.Module):
         if gr is None:                         # capture refused: eager launches from now on (use_graph is off)
             return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd))
         gr["G"].copy_(G.reshape(-1, 4, 4))
-        main = torch.cuda.current_stream()
-        timing = self.loop_timing is not None          # measurement hook (tools/loop_overlap.py): when does each half run?
-        fork = torch.cuda.Event(enable_timing=timing)
-        fork.record(main)
-        marks = [fork]
-        for graph, st in gr["graphs"]:          # one linear graph per batch half, replayed on its own stream
-            if st is not main:
-                st.wait_event(fork)
-            with torch.cuda.stream(st):
-                if timing:
-                    e0 = torch.cuda.Event(enable_timing=True)
-                    e0.record(st)
-                    marks.append(e0)
-                graph.replay()
-                j = torch.cuda.Event(enable_timing=timing)
-                j.record(st)
-                marks.append(j)
-            if st is not main:
-                main.wait_event(j)
-        if timing:
-            self.loop_timing.append(marks)
+
+        def replay(graph):
+            yield graph.replay()
+
+        # one linear graph per batch half, replayed on its own stream
+        streams.run_interleaved([(replay(graph), st) for graph, st in gr["graphs"]], torch.cuda.current_stream())
         # the output buffers belong to the graph record and are overwritten by the next replay: the caller gets its own
         # copies (the reference returns distinct tensors per iteration): two device copies per OUTER iteration
         if rgbd is not None:
@@ -434,11 +411,7 @@ class PoseRefiner(nn.Module):
         try:
             Gs = G.reshape(-1, 4, 4).clone()
             main = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):                  # warm-up on a side stream: weight packing, allocator, caches
-                self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, rgbd)
-            main.wait_stream(side)
+            streams.warm_up(lambda: self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, rgbd))      # weight packing, allocator, caches
             eng.state_restore(snap)
             bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd)
             hv = eng.halves(B)
@@ -447,12 +420,11 @@ class PoseRefiner(nn.Module):
             for k, (b0, b1) in enumerate(hv):
                 # both halves replay on pool streams, never on the caller's (default) stream: a graph launched into the
                 # default stream did not overlap with the other half's graph at all (r02: HIP-event timing of the replays)
-                st = eng._stream(dev, k) if len(hv) > 1 else main
+                st = streams.helper_stream(dev, k) if len(hv) > 1 else main
                 graph = torch.cuda.CUDAGraph()
                 cap = torch.cuda.Stream()                  # (torch captures on a side stream of its own and replays on the current one)
                 with torch.cuda.graph(graph, stream=cap):
-                    for _ in self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd):
-                        pass
+                    streams.drain(self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd))
                 graphs.append((graph, st))
             return dict(key=key, graphs=graphs, G=Gs, bufs=bufs)
         except Exception as e:                             # noqa: BLE001 -- any capture failure means "run eagerly"
@@ -488,8 +460,7 @@ class PoseRefiner(nn.Module):
         if getattr(self.renderer, "occlusion", None) == "frame":     # the pairs of the batch, checked and uploaded once per forward
             views_kw["occlusion_pairs"] = ops.OcclusionPairs(image_index, Ts.G.shape[0], intrinsics.device)
         if image is not None and image.is_cuda or intrinsics.is_cuda:
-            from .streams import reserve
-            reserve(intrinsics.device)        # bind the concurrent streams to distinct hardware queues before anything else
+            streams.reserve(intrinsics.device)        # bind the concurrent streams to distinct hardware queues before anything else
             ops.range_guard_arm(intrinsics.device)
         self._refresh()
         cfg = self.cfg
@@ -516,7 +487,7 @@ class PoseRefiner(nn.Module):
             if ren_iter == 1 and self.profile_rec is not None:          # measurement hook: only the FIRST outer iteration is
                 ops.profile_end(self.profile_rec)                       # event-instrumented (eager), the others replay graphs
                 self.profile_rec = None
-            fused_pose = self.fused and Ti.G.is_cuda and self.legacy and Ti.G.shape == Tij.G.shape and os.environ.get("RNNPOSE_FUSED_POSE", "1") != "0"
+            fused_pose = self.fused and Ti.G.is_cuda and self.legacy and Ti.G.shape == Tij.G.shape and env.flag("RNNPOSE_FUSED_POSE", True)
             if fused_pose:       # r06: :241-244 as ONE launch (ops.se3_outer_update: bit-identical to the three it replaces)
                 Ti_G, Tij_G = ops.se3_outer_update(Tij.G, Ti.G, self.literal_legacy_pose)
                 Ti = Ti.__class__(matrix=Ti_G, internal=Ti.internal)

@@ -7,6 +7,8 @@ corr_weight, compiled by plain -O3 into packed fp32 instructions (v_pk_mul_f32 /
 plain-HIP probe (tools/probes/pk_f32_vs_mfma.hip) shows the same between a packed-fp32 kernel and a 16x16x32 MFMA loop, and never for
 scalar fp32.  The library is built with -fno-slp-vectorize since (tests/test_isa_guard.py guards the ISA); these tests guard the
 behaviour: "one deterministic sequence per image" (model/PoseRefiner.py:315-362) whatever else the chip is doing."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -51,9 +53,10 @@ def _inputs(B, H, W):
     return _INPUTS[key]
 
 
-def _instance_outputs(ops, B, H, W, iters, use_graph, encoder=False):
+def _instance_outputs(ops, B, H, W, iters, use_graph, encoder=False, one_stream=False):
     """One FRESH PoseRefiner on fixed inputs -> {name: tensor} of every per-iteration output (flow map, weight map, H, b, xi, G) plus
-    the number of pixels whose recorded weight is not the weight of the recorded flow map."""
+    the number of pixels whose recorded weight is not the weight of the recorded flow map.
+    one_stream: the calls run inside ops.profile(), which puts every launch on the caller's stream (and keeps the loop eager)."""
     from rnnpose_amd.pose_refiner import PoseRefiner, SyntheticRenderer, default_config
     from rnnpose_amd.transformation import SE3Sequence
     d = _inputs(B, H, W)
@@ -66,9 +69,10 @@ def _instance_outputs(ops, B, H, W, iters, use_graph, encoder=False):
     ref = PoseRefiner(default_config(RENDER_ITER_COUNT=1, ITER_COUNT=iters, OPTIM_ITER_COUNT=1), renderer=SyntheticRenderer(**kw),
                       use_graph=use_graph).cuda().eval()
     ref.cf_net.update_block.load_state_dict({k: torch.from_numpy(v) for k, v in syn.make_module_weights(orc.UPDATE_BLOCK_SHAPES, seed=0).items()})
-    out = ref(None, SE3Sequence(matrix=d["G0"].clone()), d["K"])
-    if use_graph:                      # the first call captured (and ran eagerly while warming up): the replayed result is the second one
+    with ops.profile() if one_stream else contextlib.nullcontext():
         out = ref(None, SE3Sequence(matrix=d["G0"].clone()), d["K"])
+        if use_graph:                  # the first call captured (and ran eagerly while warming up): the replayed result is the second one
+            out = ref(None, SE3Sequence(matrix=d["G0"].clone()), d["K"])
     torch.cuda.synchronize()
     res = {"flow_last": out["flow_last"].clone(), "Ti": out["Ti_pred"].G.clone(), "weight": out["weight"].clone()}
     for i, T in enumerate(ref.residual_pose_history):
@@ -163,6 +167,70 @@ def test_coordinates_formed_inside_their_consumers_change_no_bit(ops, monkeypatc
         assert o["_weight_mismatch"] == 0
         outs.append(o)
     bad = [k for k in outs[0] if not k.startswith("_") and not torch.equal(outs[0][k], outs[1][k])]
+    assert not bad, bad
+
+
+# ---- a lost fork or join: the launches on their helper streams against the SAME launches on one stream ---------------------------------
+# (rnnpose_amd/streams.py is the one place that forks and joins; tests/test_stream_schedule.py pins what it enqueues.  These runs catch
+# a dropped dependency that happens to bite -- a pass does not prove that no race exists.)
+
+@pytest.mark.parametrize("split_out", [False, True])
+@pytest.mark.parametrize("schedule", ["stream_per_set", "two_batch_parts"])
+def test_encoder_on_helper_streams_equals_the_same_launches_on_one_stream(ops, schedule, split_out):
+    """Two image sets of (2,3,96,128): one stream per set, or the concatenated batch in two parts on two streams -- against the same call
+    inside ops.profile(), in both output forms."""
+    from rnnpose_amd.cfnet import ImageFeaEncoder
+    d = _inputs(2, 96, 128)
+    torch.manual_seed(0)
+    eng = ImageFeaEncoder().cuda().eval().engine()
+    if schedule == "stream_per_set":
+        eng.merge_sets = False
+    else:
+        eng.merge_sets, eng.split_batch, eng.parts = True, True, 2
+    run = lambda: eng([d["img1"], d["img2"]], normalize=True, split_out=split_out)
+    many = run()
+    with ops.profile():
+        one = run()
+    torch.cuda.synchronize()
+    bits = lambda t: (t.data if split_out else t).view(torch.int32)
+    assert bits(many).shape == ((4, 12, 16, 256) if split_out else (4, 256, 12, 16))
+    assert torch.equal(bits(many), bits(one))
+
+
+LOOPS = {
+    # name: (B, environment) at 128 x 128, 1 outer x 2 inner iterations, encoder in the loop
+    "two_parts": (2, {"RNNPOSE_PARTS": "2"}),            # two one-image chains on two streams (forced: the batch is small)
+    "side_stream": (1, {"RNNPOSE_SIDE_STREAM": "1"}),    # one chain, its flow-feature / flow-head side chain on the helper stream
+}
+_EAGER = {}
+
+
+def _loop_eager(ops, monkeypatch, name):
+    """The eager run of LOOPS[name] on its helper streams (computed once, shared, never modified)."""
+    B, env = LOOPS[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    if name not in _EAGER:
+        _EAGER[name] = _instance_outputs(ops, B, 128, 128, 2, False, encoder=True)
+        assert _EAGER[name]["_chains"] == [(i, i + 1) for i in range(B)]
+    return B, _EAGER[name]
+
+
+@pytest.mark.parametrize("name", list(LOOPS))
+def test_loop_on_helper_streams_equals_the_same_launches_on_one_stream(ops, monkeypatch, name):
+    """Every per-iteration output (flow, weight, H, b, xi, G) of the eager loop, against the same refiner configuration inside ops.profile()."""
+    B, many = _loop_eager(ops, monkeypatch, name)
+    one = _instance_outputs(ops, B, 128, 128, 2, False, encoder=True, one_stream=True)
+    bad = [k for k in many if not k.startswith("_") and not torch.equal(many[k], one[k])]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", list(LOOPS))
+def test_replayed_loop_equals_the_eager_loop_on_helper_streams(ops, monkeypatch, name):
+    """The same configuration captured and replayed (second call; one graph per chain, each on a pool stream) against the eager run."""
+    B, many = _loop_eager(ops, monkeypatch, name)
+    replayed = _instance_outputs(ops, B, 128, 128, 2, True, encoder=True)
+    bad = [k for k in many if not k.startswith("_") and not torch.equal(many[k], replayed[k])]
     assert not bad, bad
 
 
