@@ -26,12 +26,14 @@ extern "C" {
 
 typedef void* rnnpose_stream_t;
 
-/* 3 (round 5): rnnpose_conv_desc_t ends with tile_stats_records (the launch checks the statistics buffer it is given);
+/* 4: rnnpose_conv_tiles_per_image and rnnpose_conv_tiles_per_image_ex are gone -- shape-only guesses at a tiling that depends on the
+ * whole descriptor; rnnpose_conv_tiles_per_image_desc is the one sizing call.
+ * 3 (round 5): rnnpose_conv_desc_t ends with tile_stats_records (the launch checks the statistics buffer it is given);
  * rnnpose_conv_tiles_per_image_desc sizes it from the descriptor itself.
  * 2 (round 4): rnnpose_conv_desc_t grew the split-tensor / K-split members, the packed weight array holds two orders
  * (rnnpose_conv_packed_halfs doubled), tile statistics are fp64, rnnpose_lm_step_* needs a zero-filled workspace: a consumer
  * built against version 1 must not pass the check. */
-#define RNNPOSE_ABI_VERSION 3
+#define RNNPOSE_ABI_VERSION 4
 #define RNNPOSE_MAX_LEVELS 4
 
 int rnnpose_abi_version(void);
@@ -267,8 +269,8 @@ typedef struct {
                                   128-row output tile, the column sums and sums of squares of the outputs (bias included)
                                   -- the instance-norm statistics pass of the encoder without re-reading the tensor
                                   (rnnpose_instnorm_tiles_nhwc_f32).  With tile_stats (or src0_mean_rstd) the output rows
-                                  are tiled PER IMAGE: tiles_per_image = rnnpose_conv_tiles_per_image(...), the last tile of an
-                                  image ragged, so no tile straddles two images. */
+                                  are tiled PER IMAGE: tiles_per_image = rnnpose_conv_tiles_per_image_desc(this descriptor), the last
+                                  tile of an image ragged, so no tile straddles two images. */
   const float* add_map;        /* optional (NULL = off): NHWC tensor added to y before the epilogue, y += add_map[pixel,
                                   add_c_offset + n] -- a per-pixel bias.  Used to hoist the part of a convolution whose input
                                   does not change between calls (the context half `inp` of the GRU input, constant over the
@@ -299,12 +301,8 @@ typedef struct {
   int tile;                    /* 0 = automatic; 1 = 128x64, 2 = 128x128 as 4 column waves, 3 = 128x128 as 2x2 waves, 4 = 128x64 with
                                   a block-deep register pipeline (3, 4: split sources only); 5 / 6 / 7 = the STRIP kernels with 160- / 32- / 96-row strips (160 / 32 / 96 output
                                   pixels x 64 / 96 / 128 columns per workgroup, weights and split-tensor activations by LDS-DMA:
-                                  stride 1, 3x3 / 1x5 / 5x1, c_out > 32, source channel counts in multiples of 32; a launch with tile_stats / src0_mean_rstd tiles every image into
-                                  rnnpose_conv_tiles_per_image_ex(..., tile, B) tiles).  The automatic choice takes 160-row strips for
-                                  these layer shapes when they give the launch >= 240 workgroups (or >= 24 per image) -- r06: 32-row strips
-                                  instead when those are at most 256 waves, 96-row strips when at most 512 (the thin layers of a
-                                  half-batch chain) --, 32-row strips for launches of <= 8192 pixels (single-image crops), else the 128-row kernels
-                                  (rnnpose_conv_strip(0): never strips). */
+                                  stride 1, 3x3 / 1x5 / 5x1, c_out > 32, source channel counts in multiples of 32).  How the automatic choice picks a family
+                                  and how each family tiles an image: at rnnpose_conv_tiles_per_image_desc below. */
   void* ksplit_ws;             /* optional (NULL = off): workspace of rnnpose_conv_ksplit_workspace_bytes() bytes, 16-byte aligned,
                                   its first 1024 bytes ZERO before the first launch (the kernel leaves them zero).  With it, a
                                   stride-1 launch of few tiles (B = 1 crops: 8-64 workgroups on 256 CUs) splits its K loop over up
@@ -319,7 +317,7 @@ typedef struct {
                                   the headline shapes); every other kernel keeps the three-product form.  ~2^-11 relative per product:
                                   NOT the arithmetic of the parity tolerances. */
   int tile_stats_records;      /* with tile_stats: how many (c_out, 2) records the buffer holds.  The launch REFUSES a buffer smaller
-                                  than B * rnnpose_conv_tiles_per_image_desc(this descriptor) -- which kernel family a launch takes
+                                  than (ABI 3, r06: other than) B * rnnpose_conv_tiles_per_image_desc(this descriptor) -- which kernel family a launch takes
                                   (and with it the tile count: 32-row strips write four times the records of 128-row tiles) is the
                                   library's choice, so the buffer is checked where the choice is made. */
 } rnnpose_conv_desc_t;
@@ -329,26 +327,26 @@ int rnnpose_conv_ksplit(int enable);       /* measurement switch (default 1): 0 
 int rnnpose_conv_ksplit_limits(int max_tiles, int max_splits);   /* measurement: launches of <= max_tiles (default 24, <= 96) tiles
                                                                      split into <= max_splits (default 4, 2..8) ranges */
 
-/* Output tiles per image of a convolution launch = records per image of its `tile_stats`: 3x3 stride-1 layers run on 8 x 16
- * image PATCHES (ceil(W/16) * ceil(H/8) tiles per image, nine taps on one staged halo tile), everything else on runs of 128
- * output pixels (ceil(H_out*W_out/128) when tiled per image).  rnnpose_conv_spatial_tiles(0) switches the patch tiling off
- * (measurement: the r02 row-major tiling for 3x3 layers too). */
-int rnnpose_conv_tiles_per_image(int H, int W, int kh, int kw, int stride);      /* (the 128-row kernels' rule only: it does NOT size
-                                                                                      tile_stats of a tile = 0 launch since ABI 2) */
-/* Records per image of `tile_stats` for exactly the launch this descriptor describes -- the kernel choice looks at B, H, W, kh, kw,
- * stride, c_out, tile, the sources' channel counts and whether src0_mean_rstd is set (pointers are not dereferenced, dst / weights
- * may be NULL): the one sizing rule that cannot disagree with rnnpose_conv2d_nhwc_f16x3.  -1 on bad arguments. */
+/* Output tiles per image of exactly the launch this descriptor describes = records per image of its `tile_stats`.  The kernel choice looks
+ * at B, H, W, kh, kw, stride, c_out, tile, the sources' channel counts, src_hl and whether src0_mean_rstd is set (pointers are not
+ * dereferenced, dst / weights may be NULL); the launch plans itself with the same function, so the answer cannot disagree with
+ * rnnpose_conv2d_nhwc_f16x3, which requires tile_stats_records == B * (this answer).  -1 on bad arguments, and for a strip height forced
+ * (tile 5 / 6 / 7) on a launch the strip kernels cannot take.  The tiling rules:
+ *   - 128-row kernels: 3x3 stride-1 layers run on 8 x 16 image PATCHES (ceil(W/16) * ceil(H/8) tiles per image, nine taps on one staged
+ *     halo tile), everything else on runs of 128 output pixels (ceil(H_out*W_out/128) when tiled per image).  rnnpose_conv_spatial_tiles(0)
+ *     switches the patch tiling off (measurement: the r02 row-major tiling for 3x3 layers too).
+ *   - strip kernels (160 / 96 / 32 rows): 3x3 layers on ceil(W/16) * ceil(H/10) patches of 10 x 16 pixels (96 rows: 6 x 16, 32 rows:
+ *     2 x 16), 1x5 / 5x1 layers on ceil(H*W/160) runs of 160 (96, 32) pixels; stride-2 3x3 / 1x1 layers like a 3x3 layer on the OUTPUT grid.
+ *   - the automatic choice (tile 0) takes 160-row strips for stride-1 3x3 / 1x5 / 5x1 layers when they give the launch >= 240 workgroups
+ *     (or >= 24 per image with more than 8192 pixels) -- r06: 32-row strips instead when those are at most 256 waves, 96-row strips
+ *     when at most 512 (the thin layers of a half-batch chain) --, 32-row strips for launches of <= 8192 pixels (single-image crops),
+ *     else the 128-row kernels; only for sources of whole 32-channel blocks, with src0_mean_rstd only for 3x3.  Stride 2 (3x3 / 1x1, even
+ *     H and W): 160-row strips by the same counts for ONE fp32 source of whole 32-channel blocks without src0_mean_rstd.
+ *     rnnpose_conv_strip(0): never strips. */
 int rnnpose_conv_tiles_per_image_desc(const rnnpose_conv_desc_t* h_desc);
 /* fp16 MFMA products per multiply-add the launch this descriptor describes executes: 3 (fp16x3 split) or 1 (single_product honoured:
- * 160-row strips with one column tile per wave).  For flop accounting (bench.py's pipe_util); -1 on bad arguments. */
+ * 160-row strips with one column tile per wave).  For flop accounting (bench.py's pipe_util); -1 where the call above answers -1. */
 int rnnpose_conv_products_desc(const rnnpose_conv_desc_t* h_desc);
-/* The same for the kernel a launch of `batch` images with this c_out and `tile` request (0 automatic .. 7) will take: the strip
- * kernels tile an image into ceil(W/16) * ceil(H/10) patches of 10 x 16 pixels (3x3) or ceil(H*W/160) runs of 160 pixels (96-row strips: patches of 6 x 16 pixels, runs of 96; 32-row
- * strips: patches of 2 x 16 pixels, runs of 32).  Shape-only: it assumes source channel counts in multiples of 32 (launches whose
- * sources are not fall back to the 128-row kernels: use rnnpose_conv_tiles_per_image_desc).  STRIDE 2: -1 whenever the shape alone would
- * allow the strip form -- whether a stride-2 launch takes it depends on its sources: only rnnpose_conv_tiles_per_image_desc answers.
- * A launch with statistics requires tile_stats_records == B * (that answer), not merely >= (ABI 3, tightened in r06). */
-int rnnpose_conv_tiles_per_image_ex(int H, int W, int kh, int kw, int stride, int c_out, int tile, int batch);
 int rnnpose_conv_spatial_tiles(int enable);
 int rnnpose_conv_strip(int mode);          /* measurement switch: 0 = the automatic choice never takes the strip kernels, 1 = default,
                                               2 = automatic without the two-wave workgroups of 64-channel layers, 3 = two 32-column

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 3          # include/rnnpose_hip.h: RNNPOSE_ABI_VERSION of the library this front end was written against
+ABI_VERSION = 4          # include/rnnpose_hip.h: RNNPOSE_ABI_VERSION of the library this front end was written against
 LIB_PATH = os.environ.get("RNNPOSE_LIB") or os.path.join(_PKG, "lib", "librnnpose_hip.so")
 
 _p = C.c_void_p
@@ -76,8 +76,6 @@ PROTOTYPES = {
     "rnnpose_se3_outer_update_f32": (_i, [_p, _p, _i, _i, _p, _p, _p]),
     "rnnpose_gru_gate_f32": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
     "rnnpose_gru_update_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
-    "rnnpose_conv_tiles_per_image": (_i, [_i, _i, _i, _i, _i]),
-    "rnnpose_conv_tiles_per_image_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rnnpose_conv_tiles_per_image_desc": (_i, [C.POINTER(ConvDesc)]),
     "rnnpose_conv_products_desc": (_i, [C.POINTER(ConvDesc)]),
     "rnnpose_conv_spatial_tiles": (_i, [_i]),

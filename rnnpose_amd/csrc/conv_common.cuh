@@ -95,21 +95,49 @@ struct PackParams {
   float w_scale;
 };
 
-// conv_strip.hip: the strip kernels (160-row strips, operands by LDS-DMA)
-int strip_waves(int c_out);                                    // workgroup shape: 16 * (32-column tiles per wave) + waves; 0 = unsupported width
-void strip_allow_two_wave(int on);                             // measurement: two-wave workgroups (c_out <= 64) in the automatic choice (default on)
-void strip_force_ni(int ni);                                   // measurement: 0 automatic, 1 / 2 column tiles per wave
-void strip_allow_small(int on);                                // measurement: 32-row strips in the automatic choice (default on)
-void strip_allow_s2(int on);                                   // measurement: stride-2 3x3 layers on strips over parity planes (default on)
-void strip_allow_persist(int on);                              // measurement: persistent launches of the fp32-source strip forms (default OFF: slower)
-void strip_allow_small32(int on);                              // measurement: 32-row strips for launches of <= 256 waves of 160-row strips (default on)
+// ---- the dispatch: ONE policy (every switch the kernel choice reads) and ONE plan per launch (conv_igemm.hip: plan_conv) ----
+struct ConvPolicy {
+  bool spatial = true;       // 3x3 stride-1 convolutions on 8 x 16 image patches (rnnpose_conv_spatial_tiles)
+  bool strip = true;         // false: never the strip kernels (conv_strip.hip); true: automatic (rnnpose_conv_strip)
+  bool two_wave = true;      // two-wave workgroups (c_out <= 64: the encoder's 64-channel layers at 240 x 320) in the automatic choice
+  // Column tiles per wave: 1 unless forced (0: the least-waste shape over both).  The two-tile form (one wave per SIMD, 160 x 64 per wave,
+  // 14 fragment reads per 30 MFMAs instead of 12 per 15) is built, tested and SLOWER (r04, profiles/r04_strip_ni2.txt: GRU z|r at B = 8
+  // 84.6 vs 76.4 us, even with every memory operation compiled out 70 vs 56 us): a lone wave does not keep its SIMD's matrix pipe busy.
+  int ni = 1;
+  bool small = true;         // 32-row strips in the automatic choice
+  bool s2 = true;            // stride-2 3x3 layers as strips over parity planes (false: the 128-row kernel's tap-per-staging mode)
+  bool small32 = true;       // r06: 32- / 96-row strips for launches of <= 256 / 512 waves of 160-row strips (rnnpose_conv_strip(6): off)
+  bool persist = false;      // r06: persistent launches of the fp32-source forms (rnnpose_conv_strip(7): ON).  Built, bit-identical, and SLOWER: the
+                             // encoder's 64 -> 64 layer at B = 8 takes 190-255 us instead of 155-190 (profiles/r06_persistent_strips.txt) -- OFF by default
+  bool ksplit = true;        // K split of launches with few tiles when the caller provides a workspace (rnnpose_conv_ksplit)
+  int ks_max_tiles = 24, ks_max_splits = 4;      // (rnnpose_conv_ksplit_limits: measurement)
+};
+
+// How ONE launch runs: a pure function of the descriptor and the policy.  The size queries, the launch and strip_launch all read this.
+struct ConvPlan {
+  int rows;                          // kernel family: 0 = the 128-row kernels, 32 / 96 / 160 = the strip kernels of that height
+  int ni, nw;                        // strips: column tiles of 32 per wave, waves
+  bool spatial, wide, wide22, deep;  // image patches instead of pixel runs; the 128-row tile shapes (128x128 in 4 column waves / 2x2 waves, deep pipeline)
+  int U, V, su, sv, G, T, du0, dv0, stride, Uin, Vin, gkw, dvg0;      // geometry, as in KParams
+  int Ho, Wo;                        // output extents
+  bool per_image;                    // no tile straddles two images (statistics, fused normalisation, patches)
+  int tiles_per_image;               // = records per image of tile_stats
+  int sp_tx, sp_ty;                  // patches per image row / column (spatial)
+  int n_mt, n_nt;
+  unsigned nwg;                      // workgroups of the launch (K splits included; a persistent strip launch shrinks it to the chip)
+  int products;                      // fp16 MFMA products per multiply-add: 3, or 1 (single_product honoured)
+  bool persist;                      // strips: a form that has a persistent instantiation, and the policy asks for it
+  int ksplit;                        // K split: workgroups per tile (1 = none) over the caller's workspace [arrival counters | partial accumulators]
+};
+
+// conv_strip.hip: the strip kernels (160-row strips, operands by LDS-DMA).  strip_waves / strip_rows: for plan_conv only
+int strip_waves(int c_out, int ni);                            // workgroup shape: 16 * (32-column tiles per wave) + waves; 0 = unsupported width
 long long strip_s2_halfs(int c_in, int kh, int kw, int ncb, int Npad, int n_seg);   // size of the stride-2 copy of a layer's packed weights (0: none)
-// strip height (160 / 32 rows) a launch of `batch` images takes, 0 = not a strip launch; request: 0 automatic, else the height to force
-int strip_rows(int H, int W, int kh, int kw, int stride, int c_out, int batch, int request);
-int strip_tiles_per_image(int H, int W, int kh, int kw, int rows);      // output tiles per image when tiled per image (tile_stats records)
-// launches the strip kernel for the already filled parameter block (U, V, su, sv, T, dv0, segments, epilogue ...); sets the tiling
-// members.  hlin: split-tensor sources (LDS-DMA); else fp32 sources through registers (+ fused normalisation when p.in_mr).
-int strip_launch(KParams& p, int H, int W, int kh, int kw, bool hlin, bool per_image, int rows, hipStream_t st);
+// strip height (160 / 96 / 32 rows) a launch of `batch` images takes, 0 = not a strip launch; request: 0 automatic, else the height to force
+int strip_rows(const ConvPolicy& pol, int H, int W, int kh, int kw, int stride, int c_out, int batch, int request);
+// launches the strip kernel the plan names for the filled parameter block; sets off32 and, for a persistent launch, n_tiles / stagger.
+// hlin: split-tensor sources (LDS-DMA); else fp32 sources through registers (+ fused normalisation when p.in_mr).
+int strip_launch(KParams& p, const ConvPlan& pl, int kh, int kw, bool hlin, hipStream_t st);
 int strip_launch_r32(const KParams& p, int nw, int ni, bool spatial, bool hlin, bool norm, unsigned nwg, hipStream_t st);      // conv_strip_r32.hip
 int strip_launch_r96(const KParams& p, int nw, int ni, bool spatial, bool hlin, bool norm, unsigned nwg, hipStream_t st);      // conv_strip_r96.hip (r06)
 int strip_launch_p1(const KParams& p, int nw, int ni, bool spatial, bool hlin, bool norm, unsigned nwg, hipStream_t st);       // conv_strip_p1.hip: 160-row strips, single product

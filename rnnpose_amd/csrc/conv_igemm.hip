@@ -833,37 +833,149 @@ int fill_cb_tables(const int* counts, int n, unsigned char* cb_seg, short* cb_c0
 
 using namespace rpconv;
 
-static int g_conv_strip = 1;            // 0: never the strip kernels (conv_strip.hip); 1: automatic (rnnpose_conv_strip)
-static bool g_conv_spatial = true;      // 3x3 stride-1 convolutions on 8 x 16 image patches (rnnpose_conv_spatial_tiles)
-static bool g_conv_ksplit = true;       // K split of launches with few tiles when the caller provides a workspace (rnnpose_conv_ksplit)
-static int g_ks_max_tiles = 24, g_ks_max_splits = 4;      // (rnnpose_conv_ksplit_limits: measurement)
+static ConvPolicy g_policy;             // the dispatch switches (conv_common.cuh has the defaults)
 constexpr int KS_MAX_WG = 192;          // tiles x splits of a split launch
 constexpr size_t KS_CNT_BYTES = 1024;   // arrival counters (<= 96 tiles) at the head of the workspace
 
 extern "C" {
 
+// The ONE place the dispatch is decided: which kernel family and tile shape the launch `d` describes takes, its geometry, tiling,
+// products and K split.  Pointers are looked at for null-ness and alignment only.  Always fills *out (with the 128-row form where no
+// strip kernel applies: the launch's later argument checks read it); false = no launch: bad sizes, `tile` out of range, or a strip
+// height forced (tile 5 / 6 / 7) on a launch the strip kernels cannot take.
+static bool plan_conv(const rnnpose_conv_desc_t* d, const ConvPolicy& pol, ConvPlan* out) {
+  ConvPlan& pl = *out;
+  pl = ConvPlan{};
+  if (!d || d->H <= 0 || d->W <= 0 || (d->stride != 1 && d->stride != 2) || d->c_out <= 0 || d->B < 1 || d->n_src < 1 || d->n_src > 4) return false;
+  const bool tile_ok = d->tile >= 0 && d->tile <= 7;
+  const bool k33 = d->kh == 3 && d->kw == 3, k11 = d->kh == 1 && d->kw == 1, vertical = d->kw == 1 && d->kh > 1;
+  const bool norm = d->src0_mean_rstd != nullptr, hlin = d->src_hl != 0;
+  const int H = d->H, W = d->W, Npad = rp::cdiv(d->c_out, BN) * BN;
+  int ncb = 0;
+  for (int s = 0; s < d->n_src; ++s) ncb += rp::cdiv(d->src[s].c_count, BK);
+  pl.stride = d->stride;
+  pl.Ho = d->stride == 2 ? (H + 1) / 2 : H; pl.Wo = d->stride == 2 ? (W + 1) / 2 : W;
+  pl.products = 3; pl.ksplit = 1;
+  // ---- strip height.  tile 5 / 6 / 7 force 160 / 32 / 96 rows (what the sources then lack surfaces in strip_launch); the automatic choice
+  // takes strips only when the sources qualify -- whole 32-channel blocks, the fused normalisation only for 3x3 -- and otherwise falls
+  // back to the 128-row kernels, with or without tile statistics (r04 raised an error there: ADVICE).  The stride-2 parity-plane form:
+  // ONE fp32 source of whole 32-channel blocks, no fused normalisation, <= MAX_CB blocks over the four planes, 3x3 or 1x1.
+  if (tile_ok && (d->tile >= 5 || (d->tile == 0 && pol.strip))) {
+    const bool s2_ok = d->n_src == 1 && d->src[0].c_count % 32 == 0 && !hlin && !norm && 4 * (d->src[0].c_count / 32) <= MAX_CB && (k33 || k11);
+    if (d->stride == 1 || s2_ok)
+      pl.rows = strip_rows(pol, H, W, d->kh, d->kw, d->stride, d->c_out, d->B, d->tile == 5 ? 160 : d->tile == 6 ? 32 : d->tile == 7 ? 96 : 0);
+    if (d->tile == 0) {
+      for (int s = 0; s < d->n_src; ++s)
+        if (d->src[s].c_count % 32 != 0) pl.rows = 0;
+      if (norm && !k33) pl.rows = 0;
+    }
+  }
+  if (pl.rows) {
+    // ---- strip kernels (conv_strip*.hip): strips of 160 / 96 / 32 output pixels x 32 ni nw columns, operands by LDS-DMA.  3x3: patches of
+    // (rows / 16) x 16 pixels, nine taps on one staged tile; 1x5 / 5x1: runs of `rows` pixels along the tap axis.
+    const int cfg = strip_waves(d->c_out, pol.ni);
+    pl.ni = cfg >> 4; pl.nw = cfg & 15;
+    pl.spatial = k33 || d->stride == 2;
+    if (d->stride == 2) {
+      // stride-2 3x3 / 1x1 layer (r05): the four parity planes of the source as four segments of a virtual concatenation -- strided
+      // views (pixel stride 2, row stride 2 W) starting at pixels (0,0), (0,1), (1,0), (1,1) -- on the half-resolution output grid,
+      // 2 x 2 taps per plane (conv_strip.hip: pack_strip_s2_kernel has the tap table), tiled like a 3x3 layer
+      pl.U = pl.Ho; pl.V = pl.Wo; pl.su = 2 * W; pl.sv = 2; pl.Uin = H; pl.Vin = W;
+      pl.G = 1; pl.T = 4; pl.du0 = 0; pl.dv0 = 0; pl.gkw = d->kw; pl.dvg0 = -(d->kw / 2);
+    } else if (vertical) {     // column-major: fast axis = y
+      pl.U = pl.Uin = W; pl.V = pl.Vin = H; pl.su = 1; pl.sv = W;
+      pl.G = 1; pl.T = d->kh; pl.du0 = 0; pl.dv0 = -(d->kh / 2);
+    } else {                   // (3x3: source pixel of a staged row: RS_ROW_PIXEL)
+      pl.U = pl.Uin = H; pl.V = pl.Vin = W; pl.su = W; pl.sv = 1;
+      pl.G = d->kh; pl.T = k33 ? 9 : d->kw; pl.du0 = -(d->kh / 2); pl.dv0 = k33 ? 0 : -(d->kw / 2);
+    }
+    pl.per_image = pl.spatial || d->tile_stats || norm;
+    if (pl.spatial) {
+      pl.sp_tx = rp::cdiv(pl.Wo, 16); pl.sp_ty = rp::cdiv(pl.Ho, pl.rows / 16);
+      pl.tiles_per_image = pl.sp_tx * pl.sp_ty;
+    } else {
+      pl.tiles_per_image = rp::cdiv(static_cast<long long>(H) * W, pl.rows);
+    }
+    pl.n_mt = pl.per_image ? d->B * pl.tiles_per_image : rp::cdiv(static_cast<long long>(d->B) * H * W, pl.rows);
+    pl.n_nt = rp::cdiv(d->c_out, 32 * pl.ni * pl.nw);
+    pl.nwg = static_cast<unsigned>(pl.n_mt) * pl.n_nt;
+    if (d->single_product && pl.rows == 160 && pl.ni == 1 && d->stride == 1) pl.products = 1;      // (the stride-2 forms keep three products)
+    pl.persist = pol.persist && !hlin && pl.ni == 1 && pl.spatial && d->stride == 1 && pl.rows == 160 && !d->single_product;      // (the forms that have a PERSIST instantiation)
+    return true;
+  }
+  // ---- 128-row kernels
+  pl.spatial = pol.spatial && k33 && d->stride == 1;      // 8 x 16 patches, nine taps on one staged tile
+  if (d->stride == 2) {        // strided: every tap is its own group (no tap sharing), row-major tiling over the OUTPUT
+    pl.U = pl.Ho; pl.V = pl.Wo; pl.su = W; pl.sv = 1; pl.Uin = H; pl.Vin = W;
+    pl.G = d->kh * d->kw; pl.T = 1; pl.du0 = -(d->kh / 2); pl.dv0 = 0; pl.gkw = d->kw; pl.dvg0 = -(d->kw / 2);
+  } else if (vertical) {       // column-major tiling: fast axis = y
+    pl.U = pl.Uin = W; pl.V = pl.Vin = H; pl.su = 1; pl.sv = W;
+    pl.G = 1; pl.T = d->kh; pl.du0 = 0; pl.dv0 = -(d->kh / 2);
+  } else {
+    pl.U = pl.Uin = H; pl.V = pl.Vin = W; pl.su = W; pl.sv = 1;
+    pl.G = pl.spatial ? 1 : d->kh; pl.T = pl.spatial ? 9 : d->kw; pl.du0 = pl.spatial ? 0 : -(d->kh / 2); pl.dv0 = pl.spatial ? 0 : -(d->kw / 2);
+  }
+  // statistics / fused normalisation are per image: tile M per image; patches never straddle images
+  pl.per_image = pl.spatial || d->tile_stats || norm;
+  if (pl.spatial) {
+    pl.sp_tx = rp::cdiv(W, 16); pl.sp_ty = rp::cdiv(H, 8);
+    pl.tiles_per_image = pl.sp_tx * pl.sp_ty;
+  } else {
+    pl.tiles_per_image = rp::cdiv(static_cast<long long>(pl.Ho) * pl.Wo, BM);
+  }
+  pl.n_mt = pl.per_image ? d->B * pl.tiles_per_image : rp::cdiv(static_cast<long long>(d->B) * pl.Ho * pl.Wo, BM);
+  // tile width: 128 when Cout fills it and there are enough workgroups for 2 per CU, else 64.  d->tile overrides (measurement).
+  // 3x3 on patches: 128x64 as 2x2 waves unless the 4-column layout is asked for (tile shapes 3 / 4 do not apply): at 2 workgroups per
+  // CU (58 KB of LDS) the 128x128 tile's 600-odd workgroups need a second round (heads, half batch: 100 vs 80 us); at the full batch the two are equal
+  pl.wide22 = d->tile == 3 && hlin && !pl.spatial;            // 128x128 as 2x2 waves of 64x64 (NI = 2): stride-1 split-source layers only
+  pl.deep = d->tile == 4 && hlin && !pl.spatial && (pl.T == 3 || pl.T == 5);     // 128x64, weights of a whole block + two activation tiles in flight
+  if (pl.spatial) pl.wide = d->tile == 2 && d->c_out % 128 == 0 && !norm;
+  else if (d->tile == 2) pl.wide = !norm;
+  else pl.wide = d->tile != 1 && d->tile != 4 && !pl.wide22 && !norm && (d->c_out % 128 == 0) && (static_cast<long long>(pl.n_mt) * (d->c_out / 128) >= 512);
+  pl.n_nt = pl.wide || pl.wide22 ? Npad / 128 : rp::cdiv(d->c_out, 64);
+  // K split of small launches (128x64 tiles, 2x2 waves, stride 1): only with a caller-provided workspace (two chains on two
+  // streams must not share one), tiles * splits <= KS_MAX_WG, at least two channel-block iterations per split
+  // (measured per layer at B = 1, 30 x 30, profiles/r03_conv_ksplit_layers.txt: 8-24 tiles gain 15-35 %; 32-64 tiles -- GRU z|r,
+  //  heads, the hoisted inp convolutions -- lose 5-30 % to the reduction pass: not split)
+  const int tiles = pl.n_mt * pl.n_nt, nit = pl.G * ncb;
+  if (!pl.wide && !pl.wide22 && !pl.deep && d->stride == 1 && pol.ksplit && d->ksplit_ws && tiles <= pol.ks_max_tiles && nit >= 4) {
+    int ksn = pol.ks_max_splits;
+    if (ksn > nit / 2) ksn = nit / 2;
+    if (ksn * tiles > KS_MAX_WG) ksn = KS_MAX_WG / tiles;
+    const size_t need = KS_CNT_BYTES + static_cast<size_t>(tiles) * ksn * (NT * 32) * sizeof(float);     // 2 x 1 MFMA tiles of 16 registers per lane
+    if (ksn >= 2 && d->ksplit_ws_bytes >= need && reinterpret_cast<uintptr_t>(d->ksplit_ws) % 16 == 0) pl.ksplit = ksn;
+  }
+  pl.nwg = static_cast<unsigned>(pl.n_mt) * pl.n_nt * pl.ksplit;
+  return tile_ok && d->tile < 5;
+}
+
 int rnnpose_conv_spatial_tiles(int enable) {     // measurement switch: 0 = the r02 row-major tiling for 3x3 layers too
-  g_conv_spatial = enable != 0;
+  g_policy.spatial = enable != 0;
   return 0;
 }
 
-int rnnpose_conv_strip(int mode) {               // 0 = never the strip kernels, 1 = automatic (default); measurement: 2 = automatic without
-  if (mode < 0 || mode > 7) {                    // the two-wave workgroups of the 64-channel layers, 3 = two 32-column tiles per wave,
-    rp::set_error("rnnpose_conv_strip: mode 0..7");      // 4 = 160-row strips only (by the image shape: r04's first rule),
-    return 1;                                    // 5 = automatic without the stride-2 form (r05), 6 = automatic without r06's 32-row strips for
-  }                                              //     launches of <= 256 waves
-  g_conv_strip = mode != 0;
-  strip_allow_small(mode != 4);
-  strip_allow_s2(mode != 5);
-  strip_allow_small32(mode != 6);
-  strip_allow_persist(mode == 7);                // 7 = automatic WITH r06's persistent launches of the fp32-source strip forms (measured slower: off by default)
-  strip_allow_two_wave(mode != 2);
-  strip_force_ni(mode == 3 ? 2 : 1);
+int rnnpose_conv_strip(int mode) {               // which strip forms the automatic choice may take: one row of policy fields per mode
+  if (mode < 0 || mode > 7) {
+    rp::set_error("rnnpose_conv_strip: mode 0..7");
+    return 1;
+  }
+  static const struct { bool strip, two_wave; int ni; bool small, s2, small32, persist; } modes[8] = {
+      {false, true, 1, true, true, true, false},      // 0 = never the strip kernels
+      {true, true, 1, true, true, true, false},       // 1 = automatic (default)
+      {true, false, 1, true, true, true, false},      // measurement: 2 = automatic without the two-wave workgroups of the 64-channel layers
+      {true, true, 2, true, true, true, false},       // 3 = two 32-column tiles per wave
+      {true, true, 1, false, true, true, false},      // 4 = 160-row strips only (by the image shape: r04's first rule)
+      {true, true, 1, true, false, true, false},      // 5 = automatic without the stride-2 form (r05)
+      {true, true, 1, true, true, false, false},      // 6 = automatic without r06's 32- / 96-row strips for launches of <= 256 / 512 waves
+      {true, true, 1, true, true, true, true}};       // 7 = automatic WITH r06's persistent launches of the fp32-source strip forms (measured slower: off by default)
+  const auto& m = modes[mode];
+  g_policy.strip = m.strip; g_policy.two_wave = m.two_wave; g_policy.ni = m.ni; g_policy.small = m.small;
+  g_policy.s2 = m.s2; g_policy.small32 = m.small32; g_policy.persist = m.persist;
   return 0;
 }
 
 int rnnpose_conv_ksplit(int enable) {            // measurement switch: 0 = never split K
-  g_conv_ksplit = enable != 0;
+  g_policy.ksplit = enable != 0;
   return 0;
 }
 
@@ -872,7 +984,7 @@ int rnnpose_conv_ksplit_limits(int max_tiles, int max_splits) {      // measurem
     rp::set_error("rnnpose_conv_ksplit_limits: max_tiles 1..96, max_splits 2..8");
     return 1;
   }
-  g_ks_max_tiles = max_tiles; g_ks_max_splits = max_splits;
+  g_policy.ks_max_tiles = max_tiles; g_policy.ks_max_splits = max_splits;
   return 0;
 }
 
@@ -880,60 +992,14 @@ size_t rnnpose_conv_ksplit_workspace_bytes(void) {
   return KS_CNT_BYTES + static_cast<size_t>(KS_MAX_WG) * (NT * 32) * sizeof(float);
 }
 
-int rnnpose_conv_tiles_per_image(int H, int W, int kh, int kw, int stride) {
-  if (H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return -1;
-  const int Ho = stride == 2 ? (H + 1) / 2 : H, Wo = stride == 2 ? (W + 1) / 2 : W;
-  if (g_conv_spatial && kh == 3 && kw == 3 && stride == 1) return rp::cdiv(W, 16) * rp::cdiv(H, 8);
-  return rp::cdiv(static_cast<long long>(Ho) * Wo, BM);
-}
-
-// Strip height of the launch `d` describes (0: the 128-row kernels).  tile 5 / 6 force a height (errors surface in the launch); the
-// automatic choice takes strips only when the sources qualify -- whole 32-channel blocks, the fused normalisation only for 3x3 --
-// and otherwise falls back, with or without tile statistics (r04 raised an error there: ADVICE).  The ONE place this is decided.
-static int strip_tile_rows(int tile) { return tile == 5 ? 160 : (tile == 6 ? 32 : 96); }      // tile codes of the strip heights (7: r06)
-static int desc_strip_rows(const rnnpose_conv_desc_t* d) {
-  if (d->stride == 2) {      // the parity-plane form: ONE fp32 source of whole 32-channel blocks, no fused normalisation, <= MAX_CB blocks over the four planes
-    if (d->n_src != 1 || d->src[0].c_count % 32 != 0 || d->src_hl || d->src0_mean_rstd || 4 * (d->src[0].c_count / 32) > MAX_CB) return 0;
-    if (!((d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 1))) return 0;
-  }
-  if (d->tile >= 5) return strip_rows(d->H, d->W, d->kh, d->kw, d->stride, d->c_out, d->B, strip_tile_rows(d->tile));
-  if (d->tile != 0 || !g_conv_strip) return 0;
-  const int rows = strip_rows(d->H, d->W, d->kh, d->kw, d->stride, d->c_out, d->B, 0);
-  if (!rows) return 0;
-  for (int s = 0; s < d->n_src; ++s)
-    if (d->src[s].c_count % 32 != 0) return 0;
-  if (d->src0_mean_rstd && !(d->kh == 3 && d->kw == 3)) return 0;
-  return rows;
-}
-
 int rnnpose_conv_tiles_per_image_desc(const rnnpose_conv_desc_t* d) {
-  if (!d || d->H <= 0 || d->W <= 0 || (d->stride != 1 && d->stride != 2) || d->c_out <= 0 || d->tile < 0 || d->tile > 7 || d->B < 1 ||
-      d->n_src < 1 || d->n_src > 4)
-    return -1;
-  const int rows = desc_strip_rows(d);
-  if (d->tile >= 5 && rows == 0) return -1;
-  if (rows) return d->stride == 2 ? strip_tiles_per_image(d->H / 2, d->W / 2, 3, 3, rows)      // (tiles of the OUTPUT grid, 10 x 16 patches; even sizes only)
-                                  : strip_tiles_per_image(d->H, d->W, d->kh, d->kw, rows);
-  return rnnpose_conv_tiles_per_image(d->H, d->W, d->kh, d->kw, d->stride);
+  ConvPlan pl;
+  return plan_conv(d, g_policy, &pl) ? pl.tiles_per_image : -1;
 }
 
 int rnnpose_conv_products_desc(const rnnpose_conv_desc_t* d) {
-  if (!d || rnnpose_conv_tiles_per_image_desc(d) < 0) return -1;
-  const int rows = desc_strip_rows(d);
-  return (d->single_product && rows == 160 && d->stride == 1 && (strip_waves(d->c_out) >> 4) == 1) ? 1 : 3;      // (the rule of strip_launch: P1 = 160-row strips, one column tile per wave)
-}
-
-int rnnpose_conv_tiles_per_image_ex(int H, int W, int kh, int kw, int stride, int c_out, int tile, int batch) {
-  if (H <= 0 || W <= 0 || (stride != 1 && stride != 2) || c_out <= 0 || tile < 0 || tile > 7 || batch < 1) return -1;
-  int rows = 0;
-  if (tile >= 5) rows = strip_rows(H, W, kh, kw, stride, c_out, batch, strip_tile_rows(tile));
-  else if (tile == 0 && g_conv_strip) rows = strip_rows(H, W, kh, kw, stride, c_out, batch, 0);
-  if (tile >= 5 && rows == 0) return -1;
-  // stride 2: whether the launch takes the strip form also depends on its sources (one fp32 source of whole 32-channel blocks,
-  // no fused normalisation) -- a shape-only answer could size the statistics for a tiling the launch then refuses: ask _desc
-  if (rows && stride == 2) return -1;
-  if (rows) return strip_tiles_per_image(H, W, kh, kw, rows);
-  return rnnpose_conv_tiles_per_image(H, W, kh, kw, stride);
+  ConvPlan pl;
+  return plan_conv(d, g_policy, &pl) ? pl.products : -1;
 }
 
 long long rnnpose_conv_packed_halfs(int c_out, int kh, int kw, const int* h_seg_counts, int n_seg) {
@@ -1024,26 +1090,43 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
     for (int s = 1; s < d->n_src; ++s) st[s] = st[s - 1] + rp::cdiv(counts[s - 1], BK);
     p.cb1 = st[1]; p.cb2 = st[2]; p.cb3 = st[3];
   }
-  const bool vertical = (d->kw == 1 && d->kh > 1);
+  ConvPlan pl;
+  const bool planned = plan_conv(d, g_policy, &pl);
+  const bool hlin = d->src_hl != 0;
+  RP_REQUIRE(pl.spatial || (pl.T / 2 <= HALO && (pl.stride == 2 || pl.T == 1 || pl.T == 3 || pl.T == 5 || pl.T == 7)), fn, "kernel too wide for the staged halo");
+  if (d->add_map) RP_REQUIRE(d->c_out % 4 == 0 && d->add_c_stride % 4 == 0 && d->add_c_offset % 4 == 0 &&
+                                 reinterpret_cast<uintptr_t>(d->add_map) % 16 == 0, fn, "add_map: c_out % 4 == 0, 16-byte aligned, stride/offset multiples of 4");
+  // split-tensor sources / destinations (see the header): whole 8-channel groups, 32-byte aligned rows
+  if (hlin) {
+    RP_REQUIRE(d->stride == 1 && !d->src0_mean_rstd && (pl.T == 1 || pl.T == 3 || pl.T == 5 || pl.spatial), fn,
+               "split-tensor sources: stride 1, 1/3/5 taps per group, no fused normalisation");
+    for (int s = 0; s < d->n_src; ++s)
+      RP_REQUIRE(d->src[s].c_count % 8 == 0 && d->src[s].c_offset % 8 == 0 && d->src[s].c_stride % 8 == 0 &&
+                     reinterpret_cast<uintptr_t>(d->src[s].ptr) % 32 == 0, fn,
+                 "split-tensor source: channel stride/offset/count multiples of 8, 32-byte aligned");
+  }
+  if (d->dst_hl) RP_REQUIRE(d->dst_c_stride % 8 == 0 && reinterpret_cast<uintptr_t>(d->dst) % 32 == 0 && !d->tile_stats, fn,
+                            "split-form dst: channel stride multiple of 8, 32-byte aligned, no tile statistics");
+  if (d->dst2_hl) RP_REQUIRE(d->epilogue == 2 && d->dst2_c_stride % 8 == 0 && reinterpret_cast<uintptr_t>(d->dst2) % 32 == 0, fn,
+                             "split-form dst2: GRU z|r epilogue, channel stride multiple of 8, 32-byte aligned");
+  if (d->dst_split) RP_REQUIRE(d->epilogue != 2 && d->dst_split_c_stride % 8 == 0 && d->dst_split_c_offset % 4 == 0 &&
+                                   reinterpret_cast<uintptr_t>(d->dst_split) % 32 == 0, fn,
+                               "dst_split: not with the GRU z|r epilogue; channel stride multiple of 8, offset of 4, 32-byte aligned");
+  RP_REQUIRE(d->tile >= 0 && d->tile <= 7, fn, "tile must be 0 (auto), 1 (128x64), 2 (128x128, 4 column waves), 3 (128x128, 2x2 waves), 4 (128x64, deep pipeline), 5 / 6 / 7 (strips of 160 / 32 / 96 rows)");
+  if (d->tile_stats) RP_REQUIRE(d->epilogue == 0, fn, "tile_stats needs the linear epilogue");
+  RP_REQUIRE(static_cast<long long>(d->B) * pl.Ho * pl.Wo < (1LL << 31) - 256 && static_cast<long long>(d->B) * d->H * d->W < (1LL << 31) - 256, fn, "too many pixels");
+  if (d->tile_stats)       // the buffer is checked against the tiling of the kernel THIS launch takes (ABI 3)
+    RP_REQUIRE(planned && static_cast<long long>(d->tile_stats_records) == static_cast<long long>(d->B) * pl.tiles_per_image, fn,
+               "tile_stats_records must equal B * rnnpose_conv_tiles_per_image_desc(desc) (a consumer derives the tiling from the record count: "
+               "an oversized buffer would make it sum records this launch never writes): size the statistics buffer with that call");
+  if (d->tile >= 5) RP_REQUIRE(planned, fn, "strip kernels: stride 1, 3x3 / 1x5 / 5x1, c_out > 32 (32-row strips: one column tile per wave)");
+  // ---- the parameter block: the descriptor's operands, the plan's geometry and tiling
   p.B = d->B;
-  if (vertical) {           // column-major tiling: fast axis = y
-    p.U = d->W; p.V = d->H; p.su = 1; p.sv = d->W;
-    p.G = 1; p.T = d->kh; p.du0 = 0; p.dv0 = -(d->kh / 2);
-  } else {
-    p.U = d->H; p.V = d->W; p.su = d->W; p.sv = 1;
-    p.G = d->kh; p.T = d->kw; p.du0 = -(d->kh / 2); p.dv0 = -(d->kw / 2);
-  }
-  const bool spatial = g_conv_spatial && d->kh == 3 && d->kw == 3 && d->stride == 1;      // 8 x 16 patches, nine taps on one staged tile
-  if (spatial) { p.G = 1; p.T = 9; p.du0 = 0; p.dv0 = 0; }
-  p.stride = 1; p.Uin = p.U; p.Vin = p.V; p.gkw = 0; p.dvg0 = 0;
-  int Ho = d->H, Wo = d->W;
-  if (d->stride == 2) {      // strided: every tap is its own group (no tap sharing), row-major tiling over the OUTPUT
-    Ho = (d->H + 1) / 2; Wo = (d->W + 1) / 2;
-    p.stride = 2; p.Uin = d->H; p.Vin = d->W; p.su = d->W; p.sv = 1;
-    p.U = Ho; p.V = Wo;
-    p.G = d->kh * d->kw; p.T = 1; p.gkw = d->kw; p.du0 = -(d->kh / 2); p.dvg0 = -(d->kw / 2); p.dv0 = 0;
-  }
-  RP_REQUIRE(spatial || (p.T / 2 <= HALO && (p.stride == 2 || p.T == 1 || p.T == 3 || p.T == 5 || p.T == 7)), fn, "kernel too wide for the staged halo");
+  p.U = pl.U; p.V = pl.V; p.su = pl.su; p.sv = pl.sv;
+  p.G = pl.G; p.T = pl.T; p.du0 = pl.du0; p.dv0 = pl.dv0;
+  p.stride = pl.stride; p.Uin = pl.Uin; p.Vin = pl.Vin; p.gkw = pl.gkw; p.dvg0 = pl.dvg0;
+  p.tpi = pl.per_image ? pl.tiles_per_image : 0;
+  p.n_mt = pl.n_mt; p.n_nt = pl.n_nt; p.sp_tx = pl.sp_tx; p.sp_ty = pl.sp_ty;
   p.wpk = static_cast<const uint4*>(d->w_packed);
   p.Npad = rp::cdiv(d->c_out, BN) * BN;
   p.bias = d->bias; p.Cout = d->c_out;
@@ -1058,118 +1141,36 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
   p.tstats = d->tile_stats;
   p.in_mr = d->src0_mean_rstd;
   p.addm = d->add_map; p.addm_cs = d->add_c_stride; p.addm_co = d->add_c_offset;
-  if (d->add_map) RP_REQUIRE(d->c_out % 4 == 0 && d->add_c_stride % 4 == 0 && d->add_c_offset % 4 == 0 &&
-                                 reinterpret_cast<uintptr_t>(d->add_map) % 16 == 0, fn, "add_map: c_out % 4 == 0, 16-byte aligned, stride/offset multiples of 4");
   p.sat = d->src_bounded ? nullptr : rp::sat_counter();        // (split-form outputs of such a launch are not range-checked either)
-  p.ksplit = 1; p.ks_ws = nullptr; p.ks_cnt = nullptr;
-  // split-tensor sources / destinations (see the header): whole 8-channel groups, 32-byte aligned rows
-  const bool hlin = d->src_hl != 0;
-  if (hlin) {
-    RP_REQUIRE(d->stride == 1 && !d->src0_mean_rstd && (p.T == 1 || p.T == 3 || p.T == 5 || spatial), fn,
-               "split-tensor sources: stride 1, 1/3/5 taps per group, no fused normalisation");
-    for (int s = 0; s < d->n_src; ++s)
-      RP_REQUIRE(d->src[s].c_count % 8 == 0 && d->src[s].c_offset % 8 == 0 && d->src[s].c_stride % 8 == 0 &&
-                     reinterpret_cast<uintptr_t>(d->src[s].ptr) % 32 == 0, fn,
-                 "split-tensor source: channel stride/offset/count multiples of 8, 32-byte aligned");
-  }
   p.dst_hl = d->dst_hl; p.dst2_hl = d->dst2_hl;
   p.dsth = d->dst_split; p.dsth_cs = d->dst_split_c_stride; p.dsth_co = d->dst_split_c_offset;
-  if (d->dst_hl) RP_REQUIRE(d->dst_c_stride % 8 == 0 && reinterpret_cast<uintptr_t>(d->dst) % 32 == 0 && !d->tile_stats, fn,
-                            "split-form dst: channel stride multiple of 8, 32-byte aligned, no tile statistics");
-  if (d->dst2_hl) RP_REQUIRE(d->epilogue == 2 && d->dst2_c_stride % 8 == 0 && reinterpret_cast<uintptr_t>(d->dst2) % 32 == 0, fn,
-                             "split-form dst2: GRU z|r epilogue, channel stride multiple of 8, 32-byte aligned");
-  if (d->dst_split) RP_REQUIRE(d->epilogue != 2 && d->dst_split_c_stride % 8 == 0 && d->dst_split_c_offset % 4 == 0 &&
-                                   reinterpret_cast<uintptr_t>(d->dst_split) % 32 == 0, fn,
-                               "dst_split: not with the GRU z|r epilogue; channel stride multiple of 8, offset of 4, 32-byte aligned");
-  RP_REQUIRE(d->tile >= 0 && d->tile <= 7, fn, "tile must be 0 (auto), 1 (128x64), 2 (128x128, 4 column waves), 3 (128x128, 2x2 waves), 4 (128x64, deep pipeline), 5 / 6 / 7 (strips of 160 / 32 / 96 rows)");
-  if (d->tile_stats) RP_REQUIRE(d->epilogue == 0, fn, "tile_stats needs the linear epilogue");
-  const long long Mtot = static_cast<long long>(d->B) * Ho * Wo;
-  RP_REQUIRE(Mtot < (1LL << 31) - 256 && static_cast<long long>(d->B) * d->H * d->W < (1LL << 31) - 256, fn, "too many pixels");
-  {
-    // the packed array holds both orders (rnnpose_conv_packed_halfs): the strip kernels' copy sits behind the first one
-    const long long first = static_cast<long long>(d->kh) * d->kw * p.ncb * p.Npad * BK * 2;
-    p.wpk_strip = reinterpret_cast<const uint4*>(static_cast<const _Float16*>(d->w_packed) + first);
-    p.single_product = d->single_product != 0;
+  p.single_product = d->single_product != 0;
+  p.ksplit = pl.ksplit; p.ks_ws = nullptr; p.ks_cnt = nullptr;
+  if (pl.ksplit > 1) {
+    p.ks_cnt = static_cast<unsigned*>(d->ksplit_ws);
+    p.ks_ws = reinterpret_cast<float*>(static_cast<char*>(d->ksplit_ws) + KS_CNT_BYTES);
   }
-  // ---- strip kernels (conv_strip*.hip): 160- / 32-row strips, operands by LDS-DMA.  tile 5 / 6 ask for them; the automatic choice
-  // takes them for the stride-1 3x3 / 1x5 / 5x1 layers whose launch fills the chip with strips of one of the heights (strip_rows; a
-  // launch with per-image tile records tiles as rnnpose_conv_tiles_per_image_ex says for the same shape and batch)
-  if (d->tile_stats) {     // the buffer is checked against the tiling of the kernel THIS launch takes (ABI 3)
-    const int tpi = rnnpose_conv_tiles_per_image_desc(d);
-    RP_REQUIRE(tpi > 0 && static_cast<long long>(d->tile_stats_records) == static_cast<long long>(d->B) * tpi, fn,
-               "tile_stats_records must equal B * rnnpose_conv_tiles_per_image_desc(desc) (a consumer derives the tiling from the record count: "
-               "an oversized buffer would make it sum records this launch never writes): size the statistics buffer with that call");
-  }
-  {
-    const bool per_image = d->tile_stats || d->src0_mean_rstd;
-    const int rows = desc_strip_rows(d);
-    if (d->tile >= 5)
-      RP_REQUIRE(rows != 0, fn, "strip kernels: stride 1, 3x3 / 1x5 / 5x1, c_out > 32 (32-row strips: one column tile per wave)");
-    if (rows && d->stride == 2) {
-      // stride-2 3x3 layer on strips (r05): the four parity planes of the source as four segments of a virtual concatenation -- strided
-      // views (pixel stride 2, row stride 2 W) starting at pixels (0,0), (0,1), (1,0), (1,1) -- on the half-resolution output grid,
-      // 2 x 2 taps per plane (conv_strip.hip: pack_strip_s2_kernel has the tap table).  p.U / p.V are the output extents already.
+  // the packed array holds both orders (rnnpose_conv_packed_halfs): the strip kernels' copy sits behind the first one
+  const long long first = static_cast<long long>(d->kh) * d->kw * p.ncb * p.Npad * BK * 2;
+  p.wpk_strip = reinterpret_cast<const uint4*>(static_cast<const _Float16*>(d->w_packed) + first);
+  if (pl.rows) {           // (a forced strip launch whose sources do not fit surfaces its error in strip_launch)
+    if (d->stride == 2 && d->kh == 3) {      // the four parity planes of the one source as four segments, their packed copy behind the stride-1 strip copy
       const rnnpose_conv_src_t& sr = d->src[0];
       const int nb = sr.c_count / BK;
-      if (d->kh == 3) {
-        for (int k = 0; k < 4; ++k) {
-          const Seg sg{sr.ptr + (static_cast<long long>(k >> 1) * d->W + (k & 1)) * sr.c_stride, sr.c_stride, sr.c_offset, sr.c_count};
-          (k == 0 ? p.seg0 : k == 1 ? p.seg1 : k == 2 ? p.seg2 : p.seg3) = sg;
-        }
-        p.cb1 = nb; p.cb2 = 2 * nb; p.cb3 = 3 * nb; p.ncb = 4 * nb;
-        p.wpk_strip = reinterpret_cast<const uint4*>(reinterpret_cast<const _Float16*>(p.wpk_strip) + static_cast<long long>(nb) * 2 * 9 * p.Npad * 32);   // behind the stride-1 strip copy
-      }                        // (1x1: plane (0, 0) = segment 0 as it stands, one tap in four; its packed copy sits right behind the first one)
-      p.su = 2 * d->W; p.sv = 2; p.Uin = d->H; p.Vin = d->W;
-      p.G = 1; p.du0 = 0; p.dv0 = 0;
-      return strip_launch(p, Ho, Wo, d->kh, d->kw, false, per_image, rows, rp::as_stream(stream));
-    }
-    if (rows) {          // (a forced strip launch whose sources do not fit surfaces its error in strip_launch)
-      if (vertical) { p.G = 1; p.T = d->kh; p.du0 = 0; p.dv0 = -(d->kh / 2); }
-      else { p.G = d->kh; p.T = d->kw; p.du0 = -(d->kh / 2); p.dv0 = -(d->kw / 2); }
-      return strip_launch(p, d->H, d->W, d->kh, d->kw, hlin, per_image, rows, rp::as_stream(stream));
-    }
-  }
-  p.n_mt = rp::cdiv(Mtot, BM);
-  p.tpi = 0;
-  if (d->tile_stats || d->src0_mean_rstd) {      // statistics / fused normalisation are per image: tile M per image
-    p.tpi = rp::cdiv(static_cast<long long>(Ho) * Wo, BM);
-    p.n_mt = d->B * p.tpi;
-  }
-  if (spatial) {                                 // patches never straddle images: always per-image tiling
-    p.sp_tx = rp::cdiv(d->W, 16); p.sp_ty = rp::cdiv(d->H, 8);
-    p.tpi = p.sp_tx * p.sp_ty;
-    p.n_mt = d->B * p.tpi;
+      for (int k = 0; k < 4; ++k) {
+        const Seg sg{sr.ptr + (static_cast<long long>(k >> 1) * d->W + (k & 1)) * sr.c_stride, sr.c_stride, sr.c_offset, sr.c_count};
+        (k == 0 ? p.seg0 : k == 1 ? p.seg1 : k == 2 ? p.seg2 : p.seg3) = sg;
+      }
+      p.cb1 = nb; p.cb2 = 2 * nb; p.cb3 = 3 * nb; p.ncb = 4 * nb;
+      p.wpk_strip = reinterpret_cast<const uint4*>(reinterpret_cast<const _Float16*>(p.wpk_strip) + static_cast<long long>(nb) * 2 * 9 * p.Npad * 32);
+    }                      // (1x1 stride 2: plane (0, 0) = segment 0 as it stands, one tap in four; its packed copy sits right behind the first one)
+    return strip_launch(p, pl, d->kh, d->kw, hlin, rp::as_stream(stream));
   }
   if (d->src0_mean_rstd)
     RP_REQUIRE(d->n_src == 1 && d->stride == 1 && d->kh == 3 && d->kw == 3 && reinterpret_cast<uintptr_t>(d->src0_mean_rstd) % 16 == 0,
                fn, "src0_mean_rstd (fused instance norm + ReLU of the input) needs one source, a 3x3 stride-1 kernel, 16-byte alignment");
-  // tile width: 128 when Cout fills it and there are enough workgroups for 2 per CU, else 64.  d->tile overrides (measurement)
-  bool wide = !d->src0_mean_rstd && (d->c_out % 128 == 0) && (static_cast<long long>(p.n_mt) * (d->c_out / 128) >= 512);
-  bool wide22 = false;            // 128x128 as 2x2 waves of 64x64 (NI = 2): stride-1 split-source layers only
-  if (d->tile == 1) wide = false;
-  if (d->tile == 2) wide = !d->src0_mean_rstd;
-  if (d->tile == 3 && hlin && !spatial) { wide = false; wide22 = true; }
-  const bool deep = d->tile == 4 && hlin && !spatial && (p.T == 3 || p.T == 5);     // 128x64, weights of a whole block + two activation tiles in flight
-  if (d->tile == 4) wide = false;
-  const dim3 block(NT);
+  const dim3 block(NT), grid(pl.nwg);
   hipStream_t st = rp::as_stream(stream);
-  // K split of small launches (128x64 tiles, 2x2 waves, stride 1): only with a caller-provided workspace (two chains on two
-  // streams must not share one), tiles * splits <= KS_MAX_WG, at least two channel-block iterations per split
-  auto choose_ksplit = [&](int tiles, int nit) {
-    // (measured per layer at B = 1, 30 x 30, profiles/r03_conv_ksplit_layers.txt: 8-24 tiles gain 15-35 %; 32-64 tiles -- GRU z|r,
-    //  heads, the hoisted inp convolutions -- lose 5-30 % to the reduction pass: not split)
-    if (!g_conv_ksplit || !d->ksplit_ws || tiles > g_ks_max_tiles || nit < 4) return 1;
-    int ksn = g_ks_max_splits;
-    if (ksn > nit / 2) ksn = nit / 2;
-    if (ksn * tiles > KS_MAX_WG) ksn = KS_MAX_WG / tiles;
-    if (ksn < 2) return 1;
-    const size_t need = KS_CNT_BYTES + static_cast<size_t>(tiles) * ksn * (NT * 32) * sizeof(float);     // 2 x 1 MFMA tiles of 16 registers per lane
-    if (d->ksplit_ws_bytes < need || reinterpret_cast<uintptr_t>(d->ksplit_ws) % 16 != 0) return 1;
-    p.ksplit = ksn;
-    p.ks_cnt = static_cast<unsigned*>(d->ksplit_ws);
-    p.ks_ws = reinterpret_cast<float*>(static_cast<char*>(d->ksplit_ws) + KS_CNT_BYTES);
-    return ksn;
-  };
   // stride 1: the main loop unrolled over the taps of a group (T = kw, or kh for vertical kernels); stride 2: generic loop
 #define RP_LAUNCH_T(NI_, COLS4_, HL_)                                                                                   \
   switch (p.T) {                                                                                                         \
@@ -1180,34 +1181,21 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
       if constexpr (!(HL_)) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<NI_, false, COLS4_, 7, false, false>), grid, block, 0, st, p); \
       break;                                                                                                             \
   }
-  if (spatial) {                  // 3x3 stride 1: 8 x 16 patches, nine taps per staged tile (tile shapes 3 / 4 do not apply)
-    // 128x64 as 2x2 waves unless the 4-column layout is asked for: at 2 workgroups per CU (58 KB of LDS) the 128x128 tile's
-    // 600-odd workgroups need a second round (heads, half batch: 100 vs 80 us); at the full batch the two are equal
-    if (d->tile == 2 && d->c_out % 128 == 0 && !d->src0_mean_rstd) {
-      p.n_nt = p.Npad / 128;
-      const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt);
+  if (pl.spatial) {               // 3x3 stride 1: 8 x 16 patches, nine taps per staged tile
+    if (pl.wide) {
       if (hlin) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, true, 9, false, true, false, true>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, true, 9, false, false, false, true>), grid, block, 0, st, p);
     } else {
-      p.n_nt = rp::cdiv(d->c_out, 64);
-      const int ksn = choose_ksplit(p.n_mt * p.n_nt, p.ncb);
-      const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt * ksn);
       if (d->src0_mean_rstd) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, true, false, false, true>), grid, block, 0, st, p);
       else if (hlin) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, false, true, false, true>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, false, false, false, true>), grid, block, 0, st, p);
     }
-  } else if (deep) {
-    p.n_nt = rp::cdiv(d->c_out, 64);
-    const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt);
+  } else if (pl.deep) {
     if (p.T == 3) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 3, false, true, true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 5, false, true, true>), grid, block, 0, st, p);
-  } else if (wide22) {
-    p.n_nt = p.Npad / 128;
-    const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt);
+  } else if (pl.wide22) {
     RP_LAUNCH_T(2, false, true)
-  } else if (wide) {
-    p.n_nt = p.Npad / 128;
-    const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt);
+  } else if (pl.wide) {
     if (p.stride == 2) {
       hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, true, true>), grid, block, 0, st, p);
     } else if (hlin) {
@@ -1216,9 +1204,6 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
       RP_LAUNCH_T(1, true, false)
     }
   } else {
-    p.n_nt = rp::cdiv(d->c_out, 64);
-    const int ksn = p.stride == 2 ? 1 : choose_ksplit(p.n_mt * p.n_nt, p.G * p.ncb);
-    const dim3 grid(static_cast<unsigned>(p.n_mt) * p.n_nt * ksn);
     if (p.stride == 2) {
       hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, true, false>), grid, block, 0, st, p);
     } else if (d->src0_mean_rstd) {

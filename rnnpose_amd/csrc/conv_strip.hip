@@ -115,26 +115,17 @@ bool strip_kernel_shape(int kh, int kw) { return (kh == 3 && kw == 3) || (kh == 
 
 namespace rpconv {
 
-// Column tiles per wave: 1 unless forced.  The two-tile form (one wave per SIMD, 160 x 64 per wave, 14 fragment reads per 30
-// MFMAs instead of 12 per 15) is built, tested and SLOWER (r04, profiles/r04_strip_ni2.txt: GRU z|r at B = 8 84.6 vs 76.4 us, even
-// with every memory operation compiled out 70 vs 56 us): a lone wave does not keep its SIMD's matrix pipe busy.
-static int g_strip_two_wave = 1;     // two-wave workgroups (c_out <= 64: the encoder's 64-channel layers at 240 x 320) in the automatic choice
-static int g_strip_ni = 1;           // 1 / 2: column tiles per wave (strip_force_ni; 0: the least-waste shape over both)
-
-void strip_allow_two_wave(int on) { g_strip_two_wave = on; }
-void strip_force_ni(int ni) { g_strip_ni = ni; }      // (rnnpose_conv_strip: mode 1 -> 1, mode 2 -> 1, mode 3 -> 2)
-
 // workgroup shape for c_out output channels: NI column tiles of 32 per wave x NW waves; returns NI * 16 + NW (0 = unsupported).
 // c_out <= 64: two waves of one tile each (three workgroups per CU).
 // NI = 2 (one wave per SIMD, 160 x 64 per wave) wherever whole 64-column wave tiles fit; the column-tile width that wastes
 // the fewest columns, the wider one on a tie.
-int strip_waves(int c_out) {
+int strip_waves(int c_out, int ni_forced) {
   if (c_out <= 32) return 0;                          // (one-wave workgroups are not built)
-  if (c_out <= 64) return g_strip_ni == 2 ? 0 : 1 * 16 + 2;      // two waves of 32 columns: the encoder's 64-channel layers (strip_auto: large maps only)
+  if (c_out <= 64) return ni_forced == 2 ? 0 : 1 * 16 + 2;      // two waves of 32 columns: the encoder's 64-channel layers (strip_auto: large maps only)
   int best = 0, best_waste = 1 << 30;
   const int cand[5][2] = {{2, 4}, {2, 3}, {2, 2}, {1, 4}, {1, 3}};       // 256, 192, 128, 128, 96 columns
   for (const auto& c : cand) {
-    if (g_strip_ni != 0 && c[0] != g_strip_ni) continue;
+    if (ni_forced != 0 && c[0] != ni_forced) continue;
     const int wdt = 32 * c[0] * c[1];
     const int waste = rp::cdiv(c_out, wdt) * wdt - c_out;
     if (waste < best_waste) { best_waste = waste; best = c[0] * 16 + c[1]; }
@@ -142,26 +133,17 @@ int strip_waves(int c_out) {
   return best;
 }
 
-int strip_tiles_per_image(int H, int W, int kh, int kw, int rows) {
+static int strip_tiles_per_image(int H, int W, int kh, int kw, int rows) {
   if (kh == 3 && kw == 3) return rp::cdiv(W, SPW) * rp::cdiv(H, rows / 16);          // patches of (rows / 16) x 16 pixels
   return rp::cdiv(static_cast<long long>(H) * W, rows);
 }
 
-static int g_strip_small = 1;        // 32-row strips in the automatic choice (strip_allow_small)
-void strip_allow_small(int on) { g_strip_small = on; }
 #ifndef RS_MID96_WAVES
 #define RS_MID96_WAVES 512
 #endif
 #ifndef RS_SMALL32_WAVES
 #define RS_SMALL32_WAVES 256         // (measurement: -DRS_SMALL32_WAVES=512 also moves the GRU's q and the motion encoder's last layer at B = 4)
 #endif
-static int g_strip_small32 = 1;      // r06: 32-row strips for launches of <= 256 waves of 160-row strips (rnnpose_conv_strip(6): off)
-static int g_strip_persist = 0;      // r06: persistent launches of the fp32-source forms (rnnpose_conv_strip(7): ON).  Built, bit-identical, and SLOWER: the
-                                     // encoder's 64 -> 64 layer at B = 8 takes 190-255 us instead of 155-190 (profiles/r06_persistent_strips.txt) -- OFF by default
-static int g_strip_s2 = 1;           // stride-2 3x3 layers as strips over parity planes (strip_allow_s2; 0: the 128-row kernel's tap-per-staging mode)
-void strip_allow_s2(int on) { g_strip_s2 = on; }
-void strip_allow_small32(int on) { g_strip_small32 = on; }
-void strip_allow_persist(int on) { g_strip_persist = on; }
 
 // Strip height for a launch of `batch` images: 160 or 32 rows -- or 0: not a strip launch.  request: 0 = automatic, else that height
 // (tests, measurement).  160-row strips when they give the launch >= 240 workgroups (about one per CU) or, failing that, >= 24 per
@@ -170,17 +152,17 @@ void strip_allow_persist(int on) { g_strip_persist = on; }
 // Measured per layer (r04, profiles/r04_strip_heights.txt): single-image crops take 12-19 us per layer on 32-row strips, 18-28 on
 // the 128-row kernel, 30-48 on 160-row strips; at 14 400 pixels (16 crops) the 128-row kernel is 0.5-1 % ahead of 32-row strips on
 // the step, at 19 200 (B = 4 of the headline) they are equal.  (64-row strips were built too: never the best of the three.)
-int strip_rows(int H, int W, int kh, int kw, int stride, int c_out, int batch, int request) {
+int strip_rows(const ConvPolicy& pol, int H, int W, int kh, int kw, int stride, int c_out, int batch, int request) {
   const bool s2_1x1 = stride == 2 && kh == 1 && kw == 1;
-  if ((stride != 1 && stride != 2) || !(strip_kernel_shape(kh, kw) || s2_1x1) || strip_waves(c_out) == 0) return 0;
-  const int cfg = strip_waves(c_out), ni = cfg >> 4, nwt = (cfg & 15) * ni;         // 32-column wave tiles per workgroup
+  if ((stride != 1 && stride != 2) || !(strip_kernel_shape(kh, kw) || s2_1x1) || strip_waves(c_out, pol.ni) == 0) return 0;
+  const int cfg = strip_waves(c_out, pol.ni), ni = cfg >> 4, nwt = (cfg & 15) * ni;         // 32-column wave tiles per workgroup
   if (stride == 2) {      // r05: the 2x2-tap form over the parity planes: 3x3 (or 1x1: one plane), even input size, 160-row strips on the OUTPUT grid, one tile per wave
-    if (!g_strip_s2 || !((kh == 3 && kw == 3) || s2_1x1) || (H & 1) || (W & 1) || ni != 1) return 0;
+    if (!pol.s2 || !((kh == 3 && kw == 3) || s2_1x1) || (H & 1) || (W & 1) || ni != 1) return 0;
     H >>= 1; W >>= 1;
     kh = kw = 3;          // (tiled like a 3x3 layer: 10 x 16 patches)
   }
   if (request != 0) return (request == 160 || ((request == 32 || request == 96) && ni == 1)) ? request : 0;
-  if ((cfg & 15) == 2 && ni == 1 && g_strip_two_wave == 0) return 0;      // (two-wave workgroups, c_out <= 64: see strip_allow_two_wave)
+  if ((cfg & 15) == 2 && ni == 1 && !pol.two_wave) return 0;      // (two-wave workgroups, c_out <= 64: ConvPolicy::two_wave)
   auto fits = [&](int rows) {
     if (ni == 2 && rows != 160) return false;         // (two tiles per wave: 160-row strips only)
     if (kh == 3) {                                    // ragged patches: at most 15 % of the rows wasted
@@ -192,18 +174,18 @@ int strip_rows(int H, int W, int kh, int kw, int stride, int c_out, int batch, i
   };
   const int ncol = rp::cdiv(c_out, 32 * nwt);
   const long long nb = batch > 0 ? batch : 1;
-  if (!g_strip_small)                                 // (measurement: r04's first rule -- 160-row strips for maps that give >= 24 per image)
+  if (!pol.small)                                 // (measurement: r04's first rule -- 160-row strips for maps that give >= 24 per image)
     return fits(160) && strip_tiles_per_image(H, W, kh, kw, 160) * ncol >= 24 ? 160 : 0;
   const long long t160 = strip_tiles_per_image(H, W, kh, kw, 160) * static_cast<long long>(ncol);
   const long long npix = nb * H * W;
   if (fits(160) && (t160 * nb >= 240 || (t160 >= 24 && npix > 8192))) {
     // r06: a launch whose 160-row strips are at most 256 WAVES (a quarter of the chip's SIMDs: convf2 128 -> 64 of a half-batch chain =
     // 120 two-wave workgroups) takes 32-row strips instead -- five times the waves; 15 vs 26 us (profiles/r05_conv_layers_alone.txt hl6 / hl5)
-    if (g_strip_small32 && stride == 1 && t160 * nb * (cfg & 15) <= RS_SMALL32_WAVES && fits(32)) return 32;
+    if (pol.small32 && stride == 1 && t160 * nb * (cfg & 15) <= RS_SMALL32_WAVES && fits(32)) return 32;
     // ... and one of at most 512 waves (half the SIMDs: the 128-column layers of a half-batch chain -- GRU q, the motion encoder's last
     // layer: 120 four-wave workgroups) 96-row strips (three 32-row tiles per wave, 6 x 16 patches): 200 workgroups; q 34 -> 25 us, conv
     // 256 -> 126 53 -> 40 us at B = 4 (profiles/r06_strip_heights.txt); at B = 8 (960 waves) the 160-row form stays ahead
-    if (g_strip_small32 && stride == 1 && t160 * nb * (cfg & 15) <= RS_MID96_WAVES && fits(96)) return 96;
+    if (pol.small32 && stride == 1 && t160 * nb * (cfg & 15) <= RS_MID96_WAVES && fits(96)) return 96;
     return 160;
   }
   if (fits(32) && npix <= 8192 && strip_tiles_per_image(H, W, kh, kw, 32) * ncol * nb >= 24) return 32;
@@ -232,18 +214,15 @@ long long strip_s2_halfs(int c_in, int kh, int kw, int ncb, int Npad, int n_seg)
   return static_cast<long long>(4 * ncb) * 2 * 4 * Npad * 32;
 }
 
-int strip_launch(KParams& p, int H, int W, int kh, int kw, bool hlin, bool per_image, int rows, hipStream_t st) {
+int strip_launch(KParams& p, const ConvPlan& pl, int kh, int kw, bool hlin, hipStream_t st) {
   const char* fn = "rnnpose_conv2d_nhwc_f16x3";
+  // (the first three are invariants of a plan with rows != 0 -- strip_rows grants no height otherwise: kept as guards, no launch reaches them)
   RP_REQUIRE((strip_kernel_shape(kh, kw) && p.stride == 1) || (p.stride == 2 && ((kh == 3 && kw == 3) || (kh == 1 && kw == 1))), fn,
              "strip kernel: 3x3, 1x5 or 5x1, stride 1; 3x3 or 1x1, stride 2");
-  if (p.stride == 2) kh = kw = 3;        // (the stride-2 forms run the 3x3 geometry: 10 x 16 patches, 2 x 2 taps)
-  const int cfg = strip_waves(p.Cout);
-  RP_REQUIRE(cfg != 0, fn, "strip kernel: c_out must exceed 32");
-  const int ni = cfg >> 4, nw = cfg & 15;
-  RP_REQUIRE(rows == 160 || ((rows == 32 || rows == 96) && ni == 1), fn, "strip kernel: strips of 160, 96 or 32 rows (two column tiles per wave: 160 only)");
-  const bool spatial = kh == 3;
+  RP_REQUIRE(pl.nw != 0, fn, "strip kernel: c_out must exceed 32");
+  RP_REQUIRE(pl.rows == 160 || ((pl.rows == 32 || pl.rows == 96) && pl.ni == 1), fn, "strip kernel: strips of 160, 96 or 32 rows (two column tiles per wave: 160 only)");
   const bool norm = p.in_mr != nullptr;
-  RP_REQUIRE(!norm || (spatial && !hlin), fn, "strip kernel: the fused normalisation is the 3x3 fp32-source form");
+  RP_REQUIRE(!norm || (pl.spatial && !hlin), fn, "strip kernel: the fused normalisation is the 3x3 fp32-source form");
   {
     const Seg* sg[4] = {&p.seg0, &p.seg1, &p.seg2, &p.seg3};
     const int nseg = p.cb3 < p.ncb ? 4 : (p.cb2 < p.ncb ? 3 : (p.cb1 < p.ncb ? 2 : 1));
@@ -253,7 +232,7 @@ int strip_launch(KParams& p, int H, int W, int kh, int kw, bool hlin, bool per_i
     }
   }
   {      // 32-bit element offsets in the fast epilogue: pixel index x channel stride of every destination / operand below 2^32
-    const long long npix = static_cast<long long>(p.B) * H * W;
+    const long long npix = static_cast<long long>(p.B) * pl.Ho * pl.Wo;
     long long cs = p.dst_cs;
     if (p.dst2 && p.dst2_cs > cs) cs = p.dst2_cs;
     if (p.dsth && p.dsth_cs > cs) cs = p.dsth_cs;
@@ -262,39 +241,24 @@ int strip_launch(KParams& p, int H, int W, int kh, int kw, bool hlin, bool per_i
     if (p.aux1 && p.aux1_cs > cs) cs = p.aux1_cs;
     p.off32 = (npix + 1) * (cs + 1) < (1LL << 32) ? 1 : 0;
   }
-  p.ksplit = 1;
-  p.n_nt = rp::cdiv(p.Cout, 32 * ni * nw);
-  RP_REQUIRE(p.n_nt * ni * nw * 32 <= p.Npad, fn, "strip kernel: column tiles exceed the packed width");
-  if (spatial) {
-    p.T = p.stride == 2 ? 4 : 9; p.dv0 = 0;
-    if (p.stride == 1) { p.Uin = p.U; p.Vin = p.V; p.su = p.V; p.sv = 1; }      // (source pixel of a staged row: RS_ROW_PIXEL; stride 2: set by the caller)
-    p.sp_tx = rp::cdiv(W, SPW); p.sp_ty = rp::cdiv(H, rows / 16);
-    p.tpi = p.sp_tx * p.sp_ty;
-    p.n_mt = p.B * p.tpi;
-  } else if (per_image) {
-    p.tpi = rp::cdiv(static_cast<long long>(H) * W, rows);
-    p.n_mt = p.B * p.tpi;
-  } else {
-    p.tpi = 0;
-    p.n_mt = rp::cdiv(static_cast<long long>(p.B) * H * W, rows);
-  }
-  unsigned nwg = static_cast<unsigned>(p.n_mt) * p.n_nt;
+  RP_REQUIRE(pl.n_nt * pl.ni * pl.nw * 32 <= p.Npad, fn, "strip kernel: column tiles exceed the packed width");
+  unsigned nwg = pl.nwg;
   // r06 (measured slower, OFF unless rnnpose_conv_strip(7)): a launch of the fp32-source forms (the encoder's
   // layers) with at least 1.5 rounds of workgroups runs PERSISTENT -- as many workgroups as the chip holds at once (two-wave workgroups:
   // four per CU, else two), each walking its share of the tile list and pulling tile t + 1's first activations towards the CU in front
-  // of tile t's epilogue (conv_strip_kernel.cuh).
+  // of tile t's epilogue (conv_strip_kernel.cuh).  (Sized here, not in the plan: it asks the device for its CU count.)
   p.n_tiles = 0;
-  if (g_strip_persist && !hlin && ni == 1 && spatial && p.stride == 1 && rows == 160 && !p.single_product) {      // (the forms that have a PERSIST instantiation)
-    const unsigned slots = static_cast<unsigned>(rp::cu_count()) * (nw == 2 ? 4u : 2u) & ~7u;
+  if (pl.persist) {
+    const unsigned slots = static_cast<unsigned>(rp::cu_count()) * (pl.nw == 2 ? 4u : 2u) & ~7u;
     if (slots >= 8 && nwg >= slots + slots / 2) { p.n_tiles = static_cast<int>(nwg); nwg = slots; }
     static const int stagger_env = getenv("RNNPOSE_STRIP_STAGGER") ? atoi(getenv("RNNPOSE_STRIP_STAGGER")) : 0;      // (measurement)
     p.stagger = stagger_env;
   }
   int bad;
-  if (rows == 160 && p.single_product && ni == 1 && p.stride == 1) bad = strip_launch_p1(p, nw, ni, spatial, hlin, norm, nwg, st);      // (the stride-2 forms keep three products)
-  else if (rows == 160) bad = strip_launch_height<5>(p, nw, ni, spatial, hlin, norm, nwg, st);
-  else if (rows == 96) bad = strip_launch_r96(p, nw, ni, spatial, hlin, norm, nwg, st);
-  else bad = strip_launch_r32(p, nw, ni, spatial, hlin, norm, nwg, st);
+  if (pl.rows == 160 && pl.products == 1) bad = strip_launch_p1(p, pl.nw, pl.ni, pl.spatial, hlin, norm, nwg, st);      // (the stride-2 forms keep three products)
+  else if (pl.rows == 160) bad = strip_launch_height<5>(p, pl.nw, pl.ni, pl.spatial, hlin, norm, nwg, st);
+  else if (pl.rows == 96) bad = strip_launch_r96(p, pl.nw, pl.ni, pl.spatial, hlin, norm, nwg, st);
+  else bad = strip_launch_r32(p, pl.nw, pl.ni, pl.spatial, hlin, norm, nwg, st);
   RP_REQUIRE(!bad, fn, "strip kernel: no kernel for this workgroup shape and strip height");
   return rp::check_launch(fn);
 }

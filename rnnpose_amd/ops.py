@@ -779,23 +779,24 @@ def single_product(enable=None) -> bool:
 
 
 def conv_tiles_per_image(H, W, kh, kw, stride=1, c_out=None, tile: int = 0, batch: int = 1, src_counts=None, fused_norm: bool = False) -> int:
-    """Records per image of a convolution's tile_stats.  128-row kernels: 3x3 stride 1 on 8 x 16 patches, else runs of 128
-    output pixels; with c_out given: for the kernel a launch of `batch` images of that width and `tile` request takes -- the strip
-    kernels (csrc/conv_strip*.hip, tile=5 / 6 / 7 or the automatic choice) tile an image into 10 / 2 / 6 x 16 patches or runs of 160 / 32 / 96 pixels.
-    src_counts (channel counts of the sources) and fused_norm (the launch passes in_norm) complete the description: sources that are
-    not whole 32-channel blocks send an automatic launch to the 128-row kernels (rnnpose_conv_tiles_per_image_desc)."""
+    """Records per image of a convolution's tile_stats = how the launch tiles (rnnpose_conv_tiles_per_image_desc: the rules are in
+    include/rnnpose_hip.h).  Without c_out: the 128-row kernels' rule (3x3 stride 1 on 8 x 16 patches, else runs of 128 output pixels);
+    with c_out: for the kernel a launch of `batch` images of that width and `tile` request takes.  src_counts (channel counts of the
+    sources) and fused_norm (the launch passes in_norm) complete the description; without src_counts one source of 32 channels stands in
+    (whole 32-channel blocks, as the strip kernels want them).  Stride 2 with c_out but without src_counts raises ValueError for every
+    shape unless `tile` forces a 128-row form (1..4): there the sources decide the kernel family, and no shape-only answer is given."""
     _apply_conv_env()
     if c_out is None:
-        return int(_lib.load().rnnpose_conv_tiles_per_image(int(H), int(W), int(kh), int(kw), int(stride)))
-    if src_counts is not None:
-        d = _lib.ConvDesc()
-        for i, c in enumerate(src_counts):
-            d.src[i] = _lib.ConvSrc(None, int(c), 0, int(c))
-        d.n_src = len(src_counts)
-        d.B, d.H, d.W, d.kh, d.kw, d.stride, d.c_out, d.tile = int(batch), int(H), int(W), int(kh), int(kw), int(stride), int(c_out), int(tile)
-        d.src0_mean_rstd = 16 if fused_norm else None        # (only its null-ness is looked at)
-        return int(_lib.load().rnnpose_conv_tiles_per_image_desc(C.byref(d)))
-    return int(_lib.load().rnnpose_conv_tiles_per_image_ex(int(H), int(W), int(kh), int(kw), int(stride), int(c_out), int(tile), int(batch)))
+        c_out, tile = 64, 1                                  # (the forced 128-row form: its tiling does not depend on the width)
+    elif src_counts is None and stride == 2 and tile not in (1, 2, 3, 4):
+        raise ValueError("conv_tiles_per_image: whether a stride-2 launch takes the strip kernels depends on its sources: pass src_counts")
+    d = _lib.ConvDesc()
+    for i, c in enumerate(src_counts or [32]):
+        d.src[i] = _lib.ConvSrc(None, int(c), 0, int(c))
+    d.n_src = len(src_counts or [32])
+    d.B, d.H, d.W, d.kh, d.kw, d.stride, d.c_out, d.tile = int(batch), int(H), int(W), int(kh), int(kw), int(stride), int(c_out), int(tile)
+    d.src0_mean_rstd = 16 if fused_norm else None        # (only its null-ness is looked at)
+    return int(_lib.load().rnnpose_conv_tiles_per_image_desc(C.byref(d)))
 
 
 _conv_env_applied = False

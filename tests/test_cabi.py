@@ -30,7 +30,7 @@ def test_header_symbols_exported_and_typed(lib):
         assert hasattr(lib, n), f"{n} declared in the header but not exported"
         assert n in _lib.PROTOTYPES, f"{n} has no ctypes prototype"
     assert sorted(_lib.PROTOTYPES) == names
-    assert lib.rnnpose_abi_version() == 3
+    assert lib.rnnpose_abi_version() == 4
 
 
 def test_gfx950_code_object_present():
@@ -134,7 +134,7 @@ def test_header_is_plain_c99_and_links_against_the_library(tmp_path):
     assert out.returncode == 0, out.stderr
     ver, total = out.stdout.split()
     n = 2 * 16 * 24
-    assert int(ver) == 3 and int(total) == n * (2 * 2 * 128 + 8 * 12 + 4 * 6 + 2 * 3)     # level 0: 2 x 2 whole patches (16 x 24 -> 16 x 32 cells)
+    assert int(ver) == 4 and int(total) == n * (2 * 2 * 128 + 8 * 12 + 4 * 6 + 2 * 3)     # level 0: 2 x 2 whole patches (16 x 24 -> 16 x 32 cells)
 
 
 def test_graft_entry_build_runs():
@@ -146,24 +146,66 @@ def test_graft_entry_build_runs():
     ge = importlib.import_module("__graft_entry__")
     ge.build()
     from rnnpose_amd import _lib
-    assert _lib.load().rnnpose_abi_version() == _lib.ABI_VERSION == 3
+    assert _lib.load().rnnpose_abi_version() == _lib.ABI_VERSION == 4
+
+
+def _conv_desc(H, W, kh, kw, stride, c_out, tile, batch, src_counts=(32,)):
+    from rnnpose_amd import _lib
+    d = _lib.ConvDesc()
+    for i, c in enumerate(src_counts):
+        d.src[i] = _lib.ConvSrc(None, c, 0, c)
+    d.n_src = len(src_counts)
+    d.B, d.H, d.W, d.kh, d.kw, d.stride, d.c_out, d.tile = batch, H, W, kh, kw, stride, c_out, tile
+    return d
 
 
 def test_conv_tiling_rule_is_a_host_function(lib):
-    """rnnpose_conv_tiles_per_image_ex (records per image of a convolution's tile statistics = how the launch will tile) runs on
+    """rnnpose_conv_tiles_per_image_desc (records per image of a convolution's tile statistics = how the launch will tile) runs on
     the host: 160-row strips (10 x 16 patches / runs of 160 pixels) when they give the launch >= 240 workgroups, 32-row strips
-    (2 x 16 / runs of 32) for launches of at most 8192 pixels, else the 128-row kernels (8 x 16 patches / runs of 128)."""
-    f = lib.rnnpose_conv_tiles_per_image_ex
+    (2 x 16 / runs of 32) for launches of at most 8192 pixels, else the 128-row kernels (8 x 16 patches / runs of 128).  Asked here for
+    one source of 32 channels (whole 32-channel blocks: the strip kernels take it)."""
+    def f(*a, **kw):
+        return lib.rnnpose_conv_tiles_per_image_desc(C.byref(_conv_desc(*a, **kw)))
     assert f(60, 80, 3, 3, 1, 192, 0, 8) == 30 and f(60, 80, 3, 3, 1, 192, 1, 8) == 40       # headline, B = 8: strips / forced 128-row
     assert f(60, 80, 3, 3, 1, 192, 0, 1) == 150 and f(60, 80, 3, 3, 1, 192, 6, 8) == 150     # one image: 32-row strips / forced
     assert f(60, 80, 1, 5, 1, 256, 0, 8) == 30 and f(60, 80, 1, 5, 1, 256, 0, 1) == 150      # linear strips: runs of 160 / 32 pixels
     assert f(30, 30, 1, 5, 1, 256, 0, 1) == 29 and f(30, 30, 3, 3, 1, 128, 0, 1) == 30       # a single LINEMOD crop: 32-row strips
     assert f(30, 30, 1, 5, 1, 256, 0, 16) == 8 and f(30, 30, 3, 3, 1, 128, 0, 16) == 8       # 16 crops (14 400 pixels): 128-row kernels
     assert f(240, 320, 3, 3, 1, 64, 0, 8) == 24 * 20                                         # encoder, 64 channels: two-wave strips
-    assert f(60, 80, 3, 3, 2, 128, 0, 8) == lib.rnnpose_conv_tiles_per_image(60, 80, 3, 3, 2)    # stride 2: never strips
+    assert f(60, 80, 3, 3, 2, 128, 0, 8) == f(60, 80, 3, 3, 2, 128, 1, 8) == 10              # stride 2, 72 strips: too few, the 128-row kernels' runs of 128 output pixels
+    # bad arguments: a strip height forced on 32 output channels, tile / batch / size / stride / source count out of range, no descriptor
     assert f(60, 80, 3, 3, 1, 32, 5, 8) == -1 and f(60, 80, 3, 3, 1, 192, 8, 8) == -1 and f(60, 80, 3, 3, 1, 192, 0, 0) == -1
+    assert f(60, 80, 3, 3, 1, 192, -1, 8) == -1 and f(0, 80, 3, 3, 1, 192, 0, 8) == -1 and f(60, 80, 3, 3, 3, 192, 0, 8) == -1
+    assert f(60, 80, 3, 3, 1, 0, 0, 8) == -1 and f(60, 80, 3, 3, 1, 192, 0, 8, src_counts=()) == -1
+    assert lib.rnnpose_conv_tiles_per_image_desc(None) == -1 and lib.rnnpose_conv_products_desc(None) == -1
+    assert lib.rnnpose_conv_products_desc(C.byref(_conv_desc(60, 80, 3, 3, 1, 32, 5, 8))) == -1
     # r06: tile code 7 = 96-row strips (6 x 16 patches / runs of 96 pixels); the automatic choice takes them when the launch's 160-row strips
     # would be at most 512 waves (the 128-column layers of a half-batch chain), 32-row strips when at most 256 waves (convf2 there)
     assert f(60, 80, 3, 3, 1, 192, 7, 8) == 50 and f(60, 80, 1, 5, 1, 128, 7, 8) == 50
     assert f(60, 80, 1, 5, 1, 128, 0, 4) == 50 and f(60, 80, 1, 5, 1, 128, 0, 8) == 30 and f(60, 80, 1, 5, 1, 256, 0, 4) == 30
     assert f(60, 80, 3, 3, 1, 126, 0, 4) == 50 and f(60, 80, 3, 3, 1, 64, 0, 4) == 150 and f(60, 80, 3, 3, 1, 64, 0, 8) == 50
+
+
+def test_conv_plan_answers_match_the_recorded_dispatch():
+    """The dispatch is one function, plan_conv (csrc/conv_igemm.hip).  tests/golden/conv_plan.npz holds what the library answered BEFORE it
+    was: tiles per image and products for a sweep of descriptors (batch, map size, kernel, stride, width, tile request, sources, fused
+    norm, split sources, single product) under every rnnpose_conv_strip mode and with the patch tiling off.  Replayed on this library:
+    every answer equal, the -1s included.  Host functions only -- nothing is launched."""
+    import importlib.util
+    import numpy as np
+    from rnnpose_amd import build
+    spec = importlib.util.spec_from_file_location("gen_golden_conv_plan", os.path.join(ROOT, "tests", "golden", "gen_golden_conv_plan.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    z = np.load(os.path.join(ROOT, "tests", "golden", "conv_plan.npz"))
+    grid = {a: z["grid_" + a] for a in gen.AXES}
+    assert len(z["passes"]) == 9 and z["tiles_per_image_desc"].shape == (9, int(np.prod([len(grid[a]) for a in gen.AXES])))
+    from rnnpose_amd import ops
+    try:
+        tiles, products = gen.sweep(build.build(), grid, z["passes"])
+    finally:
+        ops._conv_env_applied = False          # (the sweep leaves the library's defaults: RNNPOSE_* switches of this session are applied again on the next use)
+    for name, got in (("tiles_per_image_desc", tiles), ("products_desc", products)):
+        bad = np.argwhere(got != z[name])
+        assert len(bad) == 0, f"{name}: {len(bad)} answers differ, first (pass, descriptor) {bad[0].tolist()}: {got[tuple(bad[0])]} != {z[name][tuple(bad[0])]}"
+    assert (tiles < 0).any() and (products == 1).any() and (tiles > 0).any()
