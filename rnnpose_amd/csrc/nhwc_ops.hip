@@ -813,8 +813,8 @@ int rnnpose_instnorm_nhwc_f32(const float* x, int B, int HW, int C, float eps, i
                               rnnpose_stream_t stream) {
   const char* fn = "rnnpose_instnorm_nhwc_f32";
   RP_REQUIRE(x && workspace && mean_rstd && out, fn, "null pointer");
-  RP_REQUIRE(B > 0 && B < 65536 && HW > 0 && C >= 32 && C <= 256 && 1024 % C == 0 || C == 96 || C == 192, fn,
-             "C must be 32, 64, 96, 128, 192 or 256");
+  RP_REQUIRE(B > 0 && B < 65536 && HW > 0, fn, "bad size");
+  RP_REQUIRE((C >= 32 && C <= 256 && 1024 % C == 0) || C == 96 || C == 192, fn, "C must be 32, 64, 96, 128, 192 or 256");
   RP_REQUIRE(workspace_bytes >= rnnpose_instnorm_workspace_bytes(B, HW, C), fn, "workspace too small");
   const int nchunk = rp::cdiv(HW, IN_ROWS);
   hipStream_t st = rp::as_stream(stream);

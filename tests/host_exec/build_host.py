@@ -116,12 +116,27 @@ def build(outdir: str) -> str:
     extra = os.environ.get("HOSTEXEC_CXXFLAGS", "").split()       # e.g. -fsanitize=address -fno-omit-frame-pointer (see tests/host_exec/README.md)
     flags = extra + ["-x", "c++", "-std=c++20", "-O1", "-fPIC", "-pthread", "-D__HIP_PLATFORM_AMD__", "-DNDEBUG", "-U_FORTIFY_SOURCE", "-w", "-I", outdir, "-I", "/opt/rocm/include",
              "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-I", HERE]
+    # HOSTEXEC_MUTATE="file::regex::replacement": one extra rewrite of the scratch copy of a source file or a header, applied before
+    # the host patches -- mutation checks ("does the tier see this bug?"), e.g. the round-5 fourth-fragment bug of the 32-row stride-2
+    # strips (profiles/r05_hostexec_mutation.txt) or the glue kernels' walks (profiles/glue_edges_mutation.txt)
+    mutate = os.environ.get("HOSTEXEC_MUTATE", "")
+    if mutate and mutate.split("::")[0] not in SOURCES + STRIP_SOURCES + list(HEADER_PATCHES):
+        raise RuntimeError(f"HOSTEXEC_MUTATE names {mutate.split('::')[0]!r}: not one of SOURCES, STRIP_SOURCES or the patched headers")
+
+    def mutated(name, txt):
+        if not mutate or mutate.split("::")[0] != name:
+            return txt
+        _, rx, rep = mutate.split("::")
+        txt, n = re.subn(rx, lambda m: rep, txt)
+        if n != 1:
+            raise RuntimeError(f"HOSTEXEC_MUTATE matched {n} places")
+        return txt
     units = []
     for name in SOURCES:
         src = os.path.join(CSRC, name)
-        if name in PATCHES:
-            txt = open(src).read()
-            for rx, rep, hits in PATCHES[name]:
+        if name in PATCHES or (mutate and mutate.split("::")[0] == name):
+            txt = mutated(name, open(src).read())
+            for rx, rep, hits in PATCHES.get(name, []):
                 txt, n = re.subn(rx, rep if '\\1' in rep else (lambda m, rep=rep: rep), txt)
                 if n != hits:
                     raise RuntimeError(f"host-exec patch of {name}: {rx!r} matched {n} places, expected {hits}")
@@ -130,16 +145,8 @@ def build(outdir: str) -> str:
         tu = os.path.join(outdir, name + ".host.cpp")
         open(tu, "w").write(f'#include "harness.hpp"\n#include "{src}"\n')
         units.append(tu)
-    # HOSTEXEC_MUTATE="file::regex::replacement": one extra rewrite of a header's scratch copy -- mutation checks ("does the tier see this
-    # bug?"), e.g. the round-5 fourth-fragment bug of the 32-row stride-2 strips (profiles/r05_hostexec_mutation.txt)
-    mutate = os.environ.get("HOSTEXEC_MUTATE", "")
     for name, patches in HEADER_PATCHES.items():
-        txt = open(os.path.join(CSRC, name)).read()
-        if mutate and mutate.split("::")[0] == name:
-            _, rx, rep = mutate.split("::")
-            txt, n = re.subn(rx, lambda m: rep, txt)
-            if n != 1:
-                raise RuntimeError(f"HOSTEXEC_MUTATE matched {n} places")
+        txt = mutated(name, open(os.path.join(CSRC, name)).read())
         for rx, rep, hits in patches:
             txt, n = re.subn(rx, lambda m, rep=rep: rep.replace("BACKREF1", m.group(1) if m.groups() else ""), txt, flags=re.S)
             if n != hits:
@@ -147,7 +154,7 @@ def build(outdir: str) -> str:
         open(os.path.join(outdir, name), "w").write(txt)
     for name in STRIP_SOURCES:
         cp = os.path.join(outdir, name)
-        open(cp, "w").write(open(os.path.join(CSRC, name)).read())
+        open(cp, "w").write(mutated(name, open(os.path.join(CSRC, name)).read()))
         tu = os.path.join(outdir, name + ".host.cpp")
         open(tu, "w").write(f'#include "harness.hpp"\n#include "{cp}"\n')
         units.append(tu)

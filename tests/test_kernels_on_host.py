@@ -174,6 +174,26 @@ def test_gru_pointwise_stages(host):
     assert np.abs(hout[:, :Cn] - want.numpy()).max() <= 1e-6
 
 
+def test_instnorm_nhwc_size_check_holds_for_every_channel_count(host):
+    """rnnpose_instnorm_nhwc_f32 refuses a bad B or HW whatever the channel count.  (With the channel alternatives `|| C == 96 || C == 192`
+    unparenthesised after the `&&` chain, 96 and 192 skipped the tests on B and HW: the call was refused by the launch only, with another
+    message.)  Each call returns 1 with the "bad size" text and launches nothing: every buffer keeps its sentinel.  Host library only."""
+    for B, HW, Cc in ((0, 4, 96), (1, 0, 96), (65536, 1, 192)):
+        x, out = np.full((4, Cc), 3.0, np.float32), np.full((4, Cc), 7.0, np.float32)
+        mr, ws = np.full((1, Cc, 2), 7.0, np.float32), np.full(Cc * 2, 7.0, np.float64)
+        n_ws = ws.nbytes if B < 65536 else 0        # (were the size check skipped again, the workspace check refuses B = 65536: no launch over these buffers)
+        rc = host.rnnpose_instnorm_nhwc_f32(P(x), B, HW, Cc, 1e-5, 1, None, P(ws), n_ws, P(mr), P(out), None)
+        assert rc == 1 and b"bad size" in host.rnnpose_last_error(), (B, HW, Cc, rc, host.rnnpose_last_error())
+        assert (out == 7.0).all() and (mr == 7.0).all() and (ws == 7.0).all()
+    x, out = A(syn.normal("hostexec.in", (5, 96), 3)), np.zeros((5, 96), np.float32)     # the accepted sizes still run
+    mr, ws = np.zeros((1, 96, 2), np.float32), np.zeros(96 * 2, np.float64)
+    host.call("rnnpose_instnorm_nhwc_f32", P(x), 1, 5, 96, 1e-5, 0, None, P(ws), ws.nbytes, P(mr), P(out), None)
+    want = (x - x.mean(0)) / np.sqrt(x.astype(np.float64).var(0) + 1e-5)
+    assert np.abs(out - want).max() <= 2e-6
+    assert host.rnnpose_instnorm_nhwc_f32(P(x), 1, 5, 40, 1e-5, 0, None, P(ws), ws.nbytes, P(mr), P(out), None) == 1
+    assert b"C must be" in host.rnnpose_last_error()
+
+
 # ---- the `-m gpu` parity tests themselves, against the host-executed kernels -------------------------------------------------------
 # Excluded: sizes that take the emulation minutes (full BASELINE shapes, the long refinement loops but one), tests of hipGraph replay
 # (no capture on the host) or of a real torch.cuda allocator; the strip-kernel tests are the second set (STRIP_IDS).
@@ -200,7 +220,8 @@ DESELECT = [
 ]
 FILES = ["tests/test_gpu_parity.py", "tests/test_gpu_conv.py", "tests/test_gpu_eval.py", "tests/test_zoom.py", "tests/test_raster.py",
          "tests/test_gpu_lm_geometry.py", "tests/test_gpu_raster_edges.py",      # (their large shapes carry `full_size` in their names: PARITY_K leaves them out)
-         "tests/test_gpu_zoom_edges.py"]                                         # (no large shapes: the whole module runs here)
+         "tests/test_gpu_zoom_edges.py",                                         # (no large shapes: the whole module runs here)
+         "tests/test_gpu_glue_edges.py"]
 
 # The strip convolution kernels (LDS-DMA by inline assembly on the GPU; tests/host_exec/build_host.py gives their scratch copy host
 # versions of the request / wait helpers): both strip heights, split-tensor (DMA) and fp32 (register-path) sources, 3x3 / 1x5 / 5x1,
@@ -260,7 +281,9 @@ def test_gpu_parity_tests_pass_on_the_host_executed_kernels(host_lib):
     a = _subset(host_lib, ["-k", PARITY_K] + [x for d in DESELECT for x in ("--deselect", d)] + FILES)
     b = _subset(host_lib, STRIP_IDS)
     _passed(b, len(STRIP_IDS))
-    _passed(a, 95 + 88 + 70 + 94)     # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py, 94: all of tests/test_gpu_zoom_edges.py
+    # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py, 94: all of tests/test_gpu_zoom_edges.py,
+    # 90: those of tests/test_gpu_glue_edges.py
+    _passed(a, 95 + 88 + 70 + 94 + 90)
 
 
 def test_harness_model(tmp_path):
