@@ -86,6 +86,9 @@ STRIP_SOURCES = ["conv_strip.hip", "conv_strip_r32.hip", "conv_strip_r96.hip", "
 SOURCES = ["pointwise.hip", "corr_pyramid.hip", "corr_lookup.hip", "corr_convc1.hip", "corr_alt.hip", "conv_igemm.hip", "conv1x1_resident.hip", "stem.hip",
            "nhwc_ops.hip", "eval_metrics.hip", "zoom_crop.hip", "raster.hip", "lm.hip", "mask_upsample.hip"]
 EXTRA = ["runtime_host.cpp"]
+# headers that need no host patch but may be named by HOSTEXEC_MUTATE -> the SOURCES that include them: the mutated header is written
+# next to scratch copies of those sources (quote includes look there first)
+MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"]}
 
 
 def clang() -> str:
@@ -120,8 +123,9 @@ def build(outdir: str) -> str:
     # the host patches -- mutation checks ("does the tier see this bug?"), e.g. the round-5 fourth-fragment bug of the 32-row stride-2
     # strips (profiles/r05_hostexec_mutation.txt) or the glue kernels' walks (profiles/glue_edges_mutation.txt)
     mutate = os.environ.get("HOSTEXEC_MUTATE", "")
-    if mutate and mutate.split("::")[0] not in SOURCES + STRIP_SOURCES + list(HEADER_PATCHES):
-        raise RuntimeError(f"HOSTEXEC_MUTATE names {mutate.split('::')[0]!r}: not one of SOURCES, STRIP_SOURCES or the patched headers")
+    if mutate and mutate.split("::")[0] not in SOURCES + STRIP_SOURCES + list(HEADER_PATCHES) + list(MUTABLE_HEADERS):
+        raise RuntimeError(f"HOSTEXEC_MUTATE names {mutate.split('::')[0]!r}: not one of SOURCES, STRIP_SOURCES, the patched or the mutable headers")
+    includers = MUTABLE_HEADERS.get(mutate.split("::")[0], []) if mutate else []
 
     def mutated(name, txt):
         if not mutate or mutate.split("::")[0] != name:
@@ -134,7 +138,7 @@ def build(outdir: str) -> str:
     units = []
     for name in SOURCES:
         src = os.path.join(CSRC, name)
-        if name in PATCHES or (mutate and mutate.split("::")[0] == name):
+        if name in PATCHES or name in includers or (mutate and mutate.split("::")[0] == name):
             txt = mutated(name, open(src).read())
             for rx, rep, hits in PATCHES.get(name, []):
                 txt, n = re.subn(rx, rep if '\\1' in rep else (lambda m, rep=rep: rep), txt)
@@ -145,6 +149,13 @@ def build(outdir: str) -> str:
         tu = os.path.join(outdir, name + ".host.cpp")
         open(tu, "w").write(f'#include "harness.hpp"\n#include "{src}"\n')
         units.append(tu)
+    if includers:
+        name = mutate.split("::")[0]
+        open(os.path.join(outdir, name), "w").write(mutated(name, open(os.path.join(CSRC, name)).read()))
+    for name in MUTABLE_HEADERS:                                    # (a stale mutated copy would shadow the header of an unmutated build)
+        if not includers or name != mutate.split("::")[0]:
+            if os.path.exists(os.path.join(outdir, name)):
+                os.remove(os.path.join(outdir, name))
     for name, patches in HEADER_PATCHES.items():
         txt = mutated(name, open(os.path.join(CSRC, name)).read())
         for rx, rep, hits in patches:
