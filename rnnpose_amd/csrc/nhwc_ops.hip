@@ -1217,6 +1217,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
 }
 
 // ---- max_pool (:88-104): max over the neighbour rows, the shadow row being zeros ---------------------------------------------
+// torch.max propagates a NaN; fmaxf drops one.  A NaN among the pooled rows stays: once m is NaN, `v > m` is false for every v.
 __global__ __launch_bounds__(256) void point_maxpool_kernel(const float* __restrict__ x, i64 ldx, int n_s, int c,
                                                             const int* __restrict__ idx, int n_q, int width, float* __restrict__ out,
                                                             i64 ldo) {
@@ -1229,7 +1230,7 @@ __global__ __launch_bounds__(256) void point_maxpool_kernel(const float* __restr
   for (int j = 0; j < width; ++j) {
     const int id = row[j];
     const float v = (id >= 0 && id < n_s) ? x[id * ldx + ch] : 0.f;
-    m = j == 0 ? v : fmaxf(m, v);
+    m = (j == 0 || v > m || v != v) ? v : m;
   }
   out[q * ldo + ch] = m;
 }

@@ -73,6 +73,9 @@ def np_grid_subsample(points, lengths, dl):
     for ln in lengths:
         p = points[s:s + ln]
         s += ln
+        if ln == 0:                                         # an empty cloud keeps its place in the lengths
+            lens.append(0)
+            continue
         mn, mx = p.min(0), p.max(0)
         origin = np.floor(mn * inv).astype(np.float32) * dl
         ijk = np.floor((p - origin) / dl).astype(np.int64)

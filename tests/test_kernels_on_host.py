@@ -221,7 +221,8 @@ DESELECT = [
 FILES = ["tests/test_gpu_parity.py", "tests/test_gpu_conv.py", "tests/test_gpu_eval.py", "tests/test_zoom.py", "tests/test_raster.py",
          "tests/test_gpu_lm_geometry.py", "tests/test_gpu_raster_edges.py",      # (their large shapes carry `full_size` in their names: PARITY_K leaves them out)
          "tests/test_gpu_zoom_edges.py",                                         # (no large shapes: the whole module runs here)
-         "tests/test_gpu_glue_edges.py", "tests/test_gpu_corr_edges.py"]
+         "tests/test_gpu_glue_edges.py", "tests/test_gpu_corr_edges.py",
+         "tests/test_gpu_point_edges.py"]                                        # (no large shapes either: 16384 x 40 x 70 takes the emulation under a second)
 
 # The strip convolution kernels (LDS-DMA by inline assembly on the GPU; tests/host_exec/build_host.py gives their scratch copy host
 # versions of the request / wait helpers): both strip heights, split-tensor (DMA) and fp32 (register-path) sources, 3x3 / 1x5 / 5x1,
@@ -282,8 +283,9 @@ def test_gpu_parity_tests_pass_on_the_host_executed_kernels(host_lib):
     b = _subset(host_lib, STRIP_IDS)
     _passed(b, len(STRIP_IDS))
     # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py, 94: all of tests/test_gpu_zoom_edges.py,
-    # 90: those of tests/test_gpu_glue_edges.py, 52: those of tests/test_gpu_corr_edges.py (all but the four entries of its 48 x 56 volume)
-    _passed(a, 95 + 88 + 70 + 94 + 90 + 52)
+    # 90: those of tests/test_gpu_glue_edges.py, 52: those of tests/test_gpu_corr_edges.py (all but the four entries of its 48 x 56 volume),
+    # 73: all of tests/test_gpu_point_edges.py
+    _passed(a, 95 + 88 + 70 + 94 + 90 + 52 + 73)
 
 
 def test_harness_model(tmp_path):
