@@ -682,7 +682,8 @@ int rnnpose_raster_resolve_f32(const float* verts, const int* faces, const int* 
                                float* out_zbuf, float* out_vdepth, rnnpose_stream_t stream);
 /* rnnpose_raster_resolve_tex_f32: pass 2 of a textured, per-pixel shaded render (DiffRender.render_mesh: TexturesUV on
  *   SoftPhongShader, faces_per_pixel = 1).  Workspace, geometry, attr and the three outputs as rnnpose_raster_resolve_f32 with
- *   with_color = 1 (out_attr has 3 + C channels).  The albedo of a pixel of image b:
+ *   with_color = 1 (out_attr has 3 + C channels): the two entries run one kernel body and differ in the colour alone, so depth
+ *   and attribute channels equal those of rnnpose_raster_resolve_f32 bit for bit.  The albedo of a pixel of image b:
  *     tex_hw[b] = (th, tw) > 0: the texture at uv = sum w_i uv_i (same barycentrics as the attributes), sampled as
  *       grid_sample(flip(map, H), uv * 2 - 1, bilinear, align_corners = True, padding_mode = border) -- uvs (U,2) of all meshes
  *       back to back, image b's start at row uv_off[b]; face_uvs (F,3) int32 = LOCAL uv indices, row for row with faces; tex =

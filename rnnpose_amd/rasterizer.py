@@ -19,7 +19,8 @@ With render_tex=True the first three channels are then the texture sampled at th
 TexturesUV.sample_textures) and Phong-shaded per pixel with interpolated vertex normals (csrc/raster.hip,
 rnnpose_raster_resolve_tex_f32); a batch without a textured mesh under shading="flat" keeps the vertex-colour entry point.
 
-Kernels: csrc/raster.hip (z-buffer by 64-bit atomicMin keys + per-pixel resolve) and csrc/zoom_crop.hip (vertex splat).
+Kernels: csrc/raster.hip (z-buffer by 64-bit atomicMin keys, launched through ops.raster_keys, + ONE per-pixel resolve kernel behind both
+resolve entry points -- they differ in the colour of a hit pixel only; _resolve_launch here) and csrc/zoom_crop.hip (vertex splat).
 PARITY UNPINNED against PyTorch3D (absent here): semantics documented in include/rnnpose_hip.h, checked against
 oracle/raster_oracle.py and by properties in tests/test_raster.py; textures and Phong against tests/texture_ref.py (a CPU
 restatement of PyTorch3D's chain on torch's grid_sample).  Mesh files: .obj through rnnpose_amd.mesh_io (no .ply).
@@ -243,42 +244,34 @@ class MeshRenderer:
 
     # ---- mesh rasteriser ---------------------------------------------------------------------------------------------
     def _raster(self, bt, T, K, size, near, perspective):
+        return ops.raster_keys(self.verts, self.faces, bt["vert_off"], bt["face_off"], bt["face_cnt"], bt["max_faces"], T, K, size, near,
+                               self.pixel_center, perspective)
+
+    def _resolve_launch(self, entry, bt, T, K, size, near, perspective, ws, attr, attr_off, Cc, nch, want_zbuf, want_vdepth, own):
+        """One resolve launch: the outputs allocated, then `entry` with the leading arguments both entries share, its `own` ones
+        (colour sources, shade, empty depth) and out / zbuf / vdepth / stream."""
         B, (H, W) = T.shape[0], (int(size[0]), int(size[1]))
-        n = int(_lib.load().rnnpose_raster_workspace_bytes(B, H, W))
-        ws = torch.empty(n // 8, dtype=torch.int64, device=self.device)
-        ops._launch("rnnpose_raster_mesh_f32", ops._ptr(self.verts), ops._ptr(self.faces), ops._ptr(bt["vert_off"]),
-                    ops._ptr(bt["face_off"]), ops._ptr(bt["face_cnt"]), bt["max_faces"], ops._ptr(T), ops._ptr(K), B, H, W,
-                    float(near), self.pixel_center, int(perspective), ops._ptr(ws), n, ops._stream())
-        return ws
+        new = lambda c, want: torch.empty(B, c, H, W, device=self.device, dtype=torch.float32) if want else None
+        out, zb, vd = new(nch, nch), new(1, want_zbuf), new(1, want_vdepth)
+        ops._launch(entry, ops._ptr(self.verts), ops._ptr(self.faces), ops._ptr(bt["vert_off"]), ops._ptr(bt["face_off"]), ops._ptr(T),
+                    ops._ptr(K), B, H, W, float(near), self.pixel_center, int(perspective), ops._ptr(ws), ops._ptr(attr),
+                    ops._ptr(attr_off), Cc, *own, ops._ptr(out), ops._ptr(zb), ops._ptr(vd), ops._stream())
+        return out, zb, vd
 
     def _resolve(self, bt, T, K, size, near, perspective, ws, attr=None, attr_off=None, Cc=0, with_color=False,
                  want_zbuf=False, want_vdepth=False, empty_depth=-1.0):
-        B, (H, W) = T.shape[0], (int(size[0]), int(size[1]))
-        nch = (3 if with_color else 0) + Cc
-        out = torch.empty(B, nch, H, W, device=self.device, dtype=torch.float32) if nch else None
-        zb = torch.empty(B, 1, H, W, device=self.device, dtype=torch.float32) if want_zbuf else None
-        vd = torch.empty(B, 1, H, W, device=self.device, dtype=torch.float32) if want_vdepth else None
-        ops._launch("rnnpose_raster_resolve_f32", ops._ptr(self.verts), ops._ptr(self.faces), ops._ptr(bt["vert_off"]),
-                    ops._ptr(bt["face_off"]), ops._ptr(T), ops._ptr(K), B, H, W, float(near), self.pixel_center,
-                    int(perspective), ops._ptr(ws), ops._ptr(attr), ops._ptr(attr_off), Cc,
-                    ops._ptr(self.colors) if with_color else C.c_void_p(0), int(with_color), int(self.shade),
-                    float(empty_depth), ops._ptr(out), ops._ptr(zb), ops._ptr(vd), ops._stream())
-        return out, zb, vd
+        own = (ops._ptr(self.colors) if with_color else C.c_void_p(0), int(with_color), int(self.shade), float(empty_depth))
+        return self._resolve_launch("rnnpose_raster_resolve_f32", bt, T, K, size, near, perspective, ws, attr, attr_off, Cc,
+                                    (3 if with_color else 0) + Cc, want_zbuf, want_vdepth, own)
 
     def _resolve_tex(self, bt, T, K, size, near, ws, attr, attr_off, Cc):
         """The textured resolve of __call__(render_tex=True): (B, 3 + Cc, H, W) maps and (B,1,H,W) depth (-1 = empty)."""
-        B, (H, W) = T.shape[0], (int(size[0]), int(size[1]))
         tx = self._tex
-        out = torch.empty(B, 3 + Cc, H, W, device=self.device, dtype=torch.float32)
-        zb = torch.empty(B, 1, H, W, device=self.device, dtype=torch.float32)
         shade = 0 if not self.shade else (2 if self.shading == "phong" else 1)
-        ops._launch("rnnpose_raster_resolve_tex_f32", ops._ptr(self.verts), ops._ptr(self.faces), ops._ptr(bt["vert_off"]),
-                    ops._ptr(bt["face_off"]), ops._ptr(T), ops._ptr(K), B, H, W, float(near), self.pixel_center, 1,
-                    ops._ptr(ws), ops._ptr(attr), ops._ptr(attr_off), Cc, ops._ptr(tx["albedo"]), ops._ptr(tx["uvs"]),
-                    ops._ptr(tx["face_uvs"]),
-                    ops._ptr(bt["uv_off"]), ops._ptr(tx["texels"]), ops._ptr(bt["tex_off"]), ops._ptr(bt["tex_hw"]),
-                    ops._ptr(tx["vnormals"]), shade, -1.0, ops._ptr(out), ops._ptr(zb), C.c_void_p(0), ops._stream())
-        return out, zb
+        own = (ops._ptr(tx["albedo"]), ops._ptr(tx["uvs"]), ops._ptr(tx["face_uvs"]), ops._ptr(bt["uv_off"]), ops._ptr(tx["texels"]),
+               ops._ptr(bt["tex_off"]), ops._ptr(bt["tex_hw"]), ops._ptr(tx["vnormals"]), shade, -1.0)
+        return self._resolve_launch("rnnpose_raster_resolve_tex_f32", bt, T, K, size, near, 1, ws, attr, attr_off, Cc, 3 + Cc, True, False,
+                                    own)[:2]
 
     def render_depth(self, model_names, T, K, render_image_size, near=0.1, far=6):
         """(B,1,h,w): camera z of the nearest vertex of the visible face, 0 where empty (diff_render_optim.py:327-367)."""

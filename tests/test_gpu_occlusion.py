@@ -392,6 +392,46 @@ def test_bad_pairs_through_the_c_abi_write_nothing(ops):
     assert np.all(occ == 7)                                           # refused before any launch
 
 
+def test_occluder_keys_equal_the_own_keys_of_the_occluder_under_the_same_window(ops):
+    """One face walk: object 1 z-buffered as the occluder of pair (0, 1) into window K[0] == K[1] leaves, in image 0 of the occluder
+    workspace, the depth bits of its own keys (image 1 of pass 1) at exactly the pixels those cover, with the low half 1 (= j) in place
+    of the face index; image 1 of the workspace (no pair targets it) stays empty.  No tolerance: the same arithmetic, bit for bit."""
+    from rnnpose_amd import _lib
+    names, (H, W) = ["b", "c"], (37, 53)
+    ren = renderer()
+    bt = ren._batch(names)
+    G, K = poses(2, 41), camera(2, H, W, shift=False)
+    assert K[0].tobytes() == K[1].tobytes()
+    Kd = dev(K)
+    for _ in range(12):                                               # shift object 1 until one of its faces crosses an image border
+        own = npy(ren._raster(bt, dev(G), Kd, (H, W), 0.1, perspective=True)).reshape(2, H, W)
+        if (np.concatenate([own[1, 0], own[1, -1], own[1, :, 0], own[1, :, -1]]) != -1).any():
+            break
+        G[1, 0, 3] += 0.01
+    hit = own != -1
+    assert np.concatenate([hit[1, 0], hit[1, -1], hit[1, :, 0], hit[1, :, -1]]).any(), "a face of object 1 must cross an image border"
+    assert hit[1].sum() > 0.1 * H * W and hit[0].any(), (int(hit[1].sum()), int(hit[0].sum()))
+    Gd = dev(G)
+    nbytes = int(_lib.load().rnnpose_raster_workspace_bytes(2, H, W))
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    keys = ren._raster(bt, Gd, Kd, (H, W), 0.1, perspective=True)
+    ws = torch.zeros(nbytes // 8, dtype=torch.int64, device="cuda")
+    vis = torch.empty(2, 1, H, W, device="cuda")
+    pt, po = torch.tensor([0], dtype=torch.int32).cuda(), torch.tensor([1], dtype=torch.int32).cuda()
+    rc = _lib.load().rnnpose_raster_occlusion_f32(p(ren.verts), p(ren.faces), p(bt["vert_off"]), p(bt["face_off"]), p(bt["face_cnt"]),
+                                                  bt["max_faces"], p(Gd), p(Kd), 2, H, W, 0.1, 0.5, p(pt), p(po), 1, 0.0, p(keys), p(ws),
+                                                  nbytes, p(vis), p(None), p(None), ops._stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert np.array_equal(npy(keys).reshape(2, H, W), own)
+    occ = npy(ws).reshape(2, H, W)
+    print(f"object 1 covers {int(hit[1].sum())} of {H * W} pixels")
+    assert np.array_equal(occ[0] == -1, ~hit[1])
+    assert np.array_equal(occ[0][hit[1]] >> 32, own[1][hit[1]] >> 32)
+    assert np.all(occ[0][hit[1]] & 0xffffffff == 1)
+    assert np.all(occ[1] == -1)
+
+
 # ---- 7-9: PoseRefiner / RendererAdapter / HipEpoch ---------------------------------------------------------------------------------
 H0, W0, ZS = 240, 320, (128, 160)
 

@@ -23,8 +23,9 @@ SELECT = [G + "test_occlusion_against_the_ray_caster",
           G + "test_no_pairs_gives_the_own_coverage",
           G + "test_depth_inout_changes_the_occluded_pixels_only",
           G + "test_bad_pairs_raise_on_the_host_before_any_launch",
-          G + "test_bad_pairs_through_the_c_abi_write_nothing"]
-EXPECTED = 4 + 1 + 4 + 1 + 2 + 2 + 1 + 1 + 1 + 1 + 1          # parametrised cases
+          G + "test_bad_pairs_through_the_c_abi_write_nothing",
+          G + "test_occluder_keys_equal_the_own_keys_of_the_occluder_under_the_same_window"]
+EXPECTED = 4 + 1 + 4 + 1 + 2 + 2 + 1 + 1 + 1 + 1 + 1 + 1      # parametrised cases
 
 
 def test_occlusion_gpu_tests_pass_on_the_host_executed_kernels(tmp_path_factory):
