@@ -18,27 +18,25 @@
 // others' MFMAs.  (First form of this fusion, r06: the LOOKUP staging phase in front of the unchanged resident kernel -- 71 KB, two
 // workgroups per CU, two rounds: 44.5 us against 23.2 + 18.7 for the two kernels; profiles/r06_lookup_convc1_fusion.txt.)
 // Numerics: the operations of the two-kernel path per element (fp32 taps in the same order, one split, the same MFMA sequence per block).
-#include "common.hpp"
-#include "f16x3.cuh"
+#include <type_traits>
 #include "corr_lookup.cuh"
+#include "resident_tile.cuh"
 
 namespace {
 
 using namespace rplookup;
-using rp::h8;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace rptile;
 
-constexpr int MQ = 32;          // pixels per workgroup
-constexpr int CT = 4;           // 16-column tiles per wave: Cout = 4 waves x 4 x 16 = 256
 constexpr int NCB = 11;         // 4 x 81 = 324 channels = 11 blocks of 32 (block 10: channels 320 .. 323, then zeros)
 constexpr int NSLOT = 4;        // ring of channel blocks: [hi plane 32 x 32 | lo plane] fp16 = 4 KB each
 constexpr int GP = 8;           // pixels per wave in the footprint fetch
 constexpr int SLOT_HALFS = 2 * MQ * 32;
 constexpr int RING_BYTES = NSLOT * SLOT_HALFS * 2;
 constexpr int FOOT_BYTES = MQ * FS * 4;
-constexpr int RSF = 260;                                            // epilogue staging row stride in floats (256 + 4: conflict-free)
 constexpr int EPI_BYTES = MQ * RSF * 4;
 constexpr int LDS_BYTES = RING_BYTES + FOOT_BYTES > EPI_BYTES ? RING_BYTES + FOOT_BYTES : EPI_BYTES;
+template <int V>
+using Int = std::integral_constant<int, V>;
 
 struct CParams {
   const float* pyr;             // the whole pyramid buffer (csrc/corr_pyramid.hip layout)
@@ -47,13 +45,7 @@ struct CParams {
   int N;                        // h * w
   long long p_off;              // pyramid row of pixel 0 of this launch (= first image x N)
   const uint4* wpk;             // convc1 packed by rnnpose_conv1x1_resident_pack_f16x3 (c_in = 324): record (cb * 16 + column tile) * 128 + part * 64 + lane
-  const float* bias;
-  float a_scale, out_scale;
-  float* dst;                   // (M, dcs): channels [dco, dco + 256)
-  int dcs, dco, relu;
-  long long M;
-  unsigned long long* sat;
-  int dst_hl;
+  TileOut out;                  // (resident_tile.cuh)
 };
 
 // x * s = hi + lo for ONE value: the arithmetic of rp::split4 (round to nearest, clamped at +-65504)
@@ -79,32 +71,29 @@ __global__ __launch_bounds__(8 * MQ, 3) void corr_convc1_kernel(const CParams p)
   // ---- per-thread pixels: the one whose footprint base this lane carries in the fetch (pixel GP * wave + (lane & 7) of the tile) and
   //      the one whose taps it forms (pixel tid & 31); window centres at level-0 scale
   const long long gfirst = m0 + GP * wave;
-  const long long gleft = p.M - gfirst;
+  const long long gleft = p.out.M - gfirst;
   const int gnpix = gleft >= GP ? GP : (gleft > 0 ? static_cast<int>(gleft) : 1);
-  const long long gfrow = p.p_off + (gleft > 0 ? gfirst : p.M - 1);
+  const long long gfrow = p.p_off + (gleft > 0 ? gfirst : p.out.M - 1);
   float gcx, gcy, tcx, tcy;
   int bg, pixg;
   {
-    const long long pp = gfirst + (lane & (GP - 1));
-    const long long pc = pp < p.M ? pp : p.M - 1;
-    const int b = static_cast<int>(pc / N), pix = static_cast<int>(pc - static_cast<long long>(b) * N);
-    gcx = p.coords[(static_cast<long long>(b) * 2 + 0) * N + pix];
-    gcy = p.coords[(static_cast<long long>(b) * 2 + 1) * N + pix];
-    const long long prow = p.p_off + pc;
-    bg = static_cast<int>(prow / N);
-    pixg = static_cast<int>(prow - static_cast<long long>(bg) * N);
-    const long long tp = m0 + (tid & 31);
-    const long long tc = tp < p.M ? tp : p.M - 1;
-    const int tb = static_cast<int>(tc / N), tpix = static_cast<int>(tc - static_cast<long long>(tb) * N);
-    tcx = p.coords[(static_cast<long long>(tb) * 2 + 0) * N + tpix];
-    tcy = p.coords[(static_cast<long long>(tb) * 2 + 1) * N + tpix];
+    const long long gp = gfirst + (lane & (GP - 1)), tp = m0 + (tid & 31);
+    const long long gpc = gp < p.out.M ? gp : p.out.M - 1;
+    int b, pix;
+    decode_px(gpc, N, b, pix);
+    const float2 gc = read_centre(p.coords, b, pix, N);
+    gcx = gc.x, gcy = gc.y;
+    decode_px(p.p_off + gpc, N, bg, pixg);
+    decode_px(tp < p.out.M ? tp : p.out.M - 1, N, b, pix);
+    const float2 tc = read_centre(p.coords, b, pix, N);
+    tcx = tc.x, tcy = tc.y;
   }
   const int r = tid & 31, g = tid >> 5;                       // tap phase: tile row, group of window rows: g = 0: j = 0, 1; g >= 1: j = g + 1
   const int j0 = g == 0 ? 0 : g + 1, nj = g == 0 ? 2 : 1;
   const int swz = ((r >> 2) & 1) << 1;
   int sat_n = 0;
 
-  // ---- MFMA side (csrc/conv1x1_resident.hip): 4 column tiles x 2 pixel tiles x 3 split products = 24 MFMAs per channel block
+  // ---- MFMA side (resident_tile.cuh): 4 column tiles x 2 pixel tiles x 3 split products = 24 MFMAs per channel block
   const int l15 = lane & 15, lq = lane >> 4;
   const int phys = lq ^ (((l15 >> 2) & 1) << 1);
   f32x4 acc[2][CT];
@@ -113,121 +102,53 @@ __global__ __launch_bounds__(8 * MQ, 3) void corr_convc1_kernel(const CParams p)
 #pragma unroll
     for (int j = 0; j < CT; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   uint4 bq[2][CT][2];                                                 // ring of 2 stages x column tile x (hi, lo)
-#define C_LOADB(SLOT_, CB_)                                                                       \
-  {                                                                                               \
-    const uint4* rec_ = p.wpk + (static_cast<long long>(CB_) * 16 + wave * CT) * 128 + lane;      \
-    _Pragma("unroll") for (int j = 0; j < CT; ++j) { bq[SLOT_][j][0] = rec_[j * 128]; bq[SLOT_][j][1] = rec_[j * 128 + 64]; } \
-  }
-  C_LOADB(0, 0)
-  C_LOADB(1, 1)
+  load_weights(bq[0], p.wpk, 0, wave, lane);
+  load_weights(bq[1], p.wpk, 1, wave, lane);
   __builtin_amdgcn_sched_barrier(0);
 
-  // one pyramid level: fetch -> taps -> the channel blocks [CB0_, CB1_) it completes
-#define C_LEVEL(L_, CB0_, CB1_)                                                                                           \
-  {                                                                                                                       \
-    constexpr int lvl_ = (L_);                                                                                            \
-    constexpr float inv_ = 1.0f / static_cast<float>(1 << lvl_);                                                          \
-    {                                                                                                                     \
-      int bx_, by_;                                                                                                       \
-      float ax_, ay_;                                                                                                     \
-      footprint_base(gcx * inv_, gcy * inv_, bx_, by_, ax_, ay_);                                                         \
-      gather_px<GP>(p.pyr, p.info, lvl_, N, lane, gnpix, bx_, by_, bg, pixg, gfrow, foot + (GP * wave) * FS);             \
-    }                                                                                                                     \
-    if (lvl_ == 3) {     /* block 10 = channels 320 .. 351: zeros behind channel 323 (its slot held block 6, consumed before the last barrier) */ \
-      reinterpret_cast<uint4*>(ring + ((NCB - 1) % NSLOT) * SLOT_HALFS)[tid] = make_uint4(0u, 0u, 0u, 0u);                \
-    }                                                                                                                     \
-    __syncthreads();                                                                                                      \
-    {                                                                                                                     \
-      int bx_, by_;                                                                                                       \
-      float ax_, ay_;                                                                                                     \
-      footprint_base(tcx * inv_, tcy * inv_, bx_, by_, ax_, ay_);                                                         \
-      const float w00 = (1.f - ax_) * (1.f - ay_), w10 = ax_ * (1.f - ay_), w01 = (1.f - ax_) * ay_, w11 = ax_ * ay_;     \
-      const float* f_ = foot + r * FS + j0 * FP;                                                                          \
-      float prev_[FP], cur_[FP];                                                                                          \
-      _Pragma("unroll") for (int x = 0; x < FP; ++x) prev_[x] = f_[x];                                                    \
-      _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                                                  \
-        if (jj < nj) {                                                                                                    \
-          _Pragma("unroll") for (int x = 0; x < FP; ++x) cur_[x] = f_[(jj + 1) * FP + x];                                 \
-          _Pragma("unroll") for (int i = 0; i < WIN; ++i) {         /* channel lvl * 81 + i * 9 + j (x-major window) */     \
-            const float v_ = w00 * prev_[i] + w10 * prev_[i + 1] + w01 * cur_[i] + w11 * cur_[i + 1];                     \
-            const int c_ = lvl_ * (WIN * WIN) + i * WIN + j0 + jj;                                                        \
-            const int k_ = c_ & 31;                                                                                       \
-            const int off_ = ((c_ >> 5) % NSLOT) * SLOT_HALFS + r * 32 + (((k_ >> 3) ^ swz) << 3) + (k_ & 7);             \
-            _Float16 hi_, lo_;                                                                                            \
-            split1(v_, p.a_scale, hi_, lo_);                                                                              \
-            if (p.sat) sat_n += !(fabsf(v_) <= 65504.f / p.a_scale) ? 1 : 0;                                             \
-            ring[off_] = hi_;                                                                                             \
-            ring[off_ + MQ * 32] = lo_;                                                                                   \
-          }                                                                                                               \
-          _Pragma("unroll") for (int x = 0; x < FP; ++x) prev_[x] = cur_[x];                                              \
-        }                                                                                                                 \
-      }                                                                                                                   \
-    }                                                                                                                     \
-    __syncthreads();                                                                                                      \
-    _Pragma("unroll") for (int cb = (CB0_); cb < (CB1_); ++cb) {                                                          \
-      const _Float16* sl_ = ring + (cb % NSLOT) * SLOT_HALFS;                                                             \
-      h8 ah[2], al[2];                                                                                                    \
-      _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                     \
-        ah[t] = *reinterpret_cast<const h8*>(sl_ + (16 * t + l15) * 32 + phys * 8);                                       \
-        al[t] = *reinterpret_cast<const h8*>(sl_ + MQ * 32 + (16 * t + l15) * 32 + phys * 8);                             \
-      }                                                                                                                   \
-      const int st_ = cb & 1;                                                                                             \
-      _Pragma("unroll") for (int j = 0; j < CT; ++j) {                                                                    \
-        const h8 bh = __builtin_bit_cast(h8, bq[st_][j][0]), bl = __builtin_bit_cast(h8, bq[st_][j][1]);                  \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t) acc[t][j] = rp::mfma16_c32(al[t], bh, acc[t][j]); \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t) acc[t][j] = rp::mfma16_c32(ah[t], bl, acc[t][j]); \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t) acc[t][j] = rp::mfma16_c32(ah[t], bh, acc[t][j]); \
-      }                                                                                                                   \
-      __builtin_amdgcn_sched_barrier(0);                                                                                  \
-      if (cb + 2 < NCB) C_LOADB(st_, cb + 2)                                                                              \
-      __builtin_amdgcn_sched_barrier(0);                                                                                  \
-    }                                                                                                                     \
-    __syncthreads();         /* the next level overwrites the footprints and the consumed ring slots */                    \
-  }
-  C_LEVEL(0, 0, 2)           // channels   0 ..  80: blocks 0, 1 complete (block 2 up to channel 80)
-  C_LEVEL(1, 2, 5)           // channels  81 .. 161: blocks 2, 3, 4
-  C_LEVEL(2, 5, 7)           // channels 162 .. 242: blocks 5, 6
-  C_LEVEL(3, 7, 11)          // channels 243 .. 323: blocks 7 .. 10
-#undef C_LEVEL
-#undef C_LOADB
-  if (p.sat && sat_n) atomicAdd(p.sat, static_cast<unsigned long long>(sat_n));
-
-  // ---- epilogue (csrc/conv1x1_resident.hip): accumulators -> LDS tile (aliasing ring + footprints; the last barrier above has passed) ->
-  //      16-byte stores, a whole 1-KB output row per 64 lanes
-  float* S = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int j = 0; j < CT; ++j) {
-    const int col = 64 * wave + 16 * j + l15;
-    const float b = p.bias[col];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float y = acc[t][j][e] * p.out_scale + b;
-        if (p.relu) y = fmaxf(y, 0.f);
-        S[(16 * t + 4 * lq + e) * RSF + col] = y;
-      }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int idx = tid + 256 * k;
-    const int row = idx >> 6, cq = (idx & 63) * 4;
-    const long long m = m0 + row;
-    if (m >= p.M) continue;
-    const float4 y = *reinterpret_cast<const float4*>(S + row * RSF + cq);
-    if (p.dst_hl) {               // quad cq of the row -> 8 bytes of the hi plane + 8 bytes of the lo plane of its 8-channel group
-      rp::h4 hi, lo;
-      rp::split4(y, p.a_scale, hi, lo);
-      if (p.sat && rp::quad_saturates(y, p.a_scale)) atomicAdd(p.sat, 1ull);
-      const int ch = p.dco + cq;
-      float* ph = p.dst + m * p.dcs + (ch & ~7) + ((ch >> 2) & 1) * 2;
-      *reinterpret_cast<rp::h4*>(ph) = hi;
-      *reinterpret_cast<rp::h4*>(ph + 4) = lo;
-    } else {
-      *reinterpret_cast<float4*>(p.dst + m * p.dcs + p.dco + cq) = y;
+  // one pyramid level: fetch -> taps -> the channel blocks [CB0, CB1) it completes
+  auto level = [&](auto L_, auto CB0_, auto CB1_) __attribute__((always_inline)) {
+    constexpr int lvl = decltype(L_)::value, CB0 = decltype(CB0_)::value, CB1 = decltype(CB1_)::value;
+    constexpr float inv = 1.0f / static_cast<float>(1 << lvl);
+    int bx, by;
+    float ax, ay;
+    footprint_base(gcx * inv, gcy * inv, bx, by, ax, ay);
+    gather_batches<GP>(AddrSelect{wave_maps(p.pyr, p.info, lvl, N, bg, pixg, gfrow)}, lane, gnpix, bx, by, foot + (GP * wave) * FS);
+    if (lvl == 3) {      // block 10 = channels 320 .. 351: zeros behind channel 323 (its slot held block 6, consumed before the last barrier)
+      reinterpret_cast<uint4*>(ring + ((NCB - 1) % NSLOT) * SLOT_HALFS)[tid] = make_uint4(0u, 0u, 0u, 0u);
     }
-  }
+    __syncthreads();
+    footprint_base(tcx * inv, tcy * inv, bx, by, ax, ay);
+    window_taps<2>(foot + r * FS + j0 * FP, ax, ay, nj, [&](int i, int jj, float v) {
+      const int c = lvl * (WIN * WIN) + i * WIN + j0 + jj;            // channel (x-major window) -> ring slot of its block, row r, swizzled chunk
+      const int k = c & 31;
+      const int off = ((c >> 5) % NSLOT) * SLOT_HALFS + r * 32 + (((k >> 3) ^ swz) << 3) + (k & 7);
+      _Float16 hi, lo;
+      split1(v, p.out.a_scale, hi, lo);
+      if (p.out.sat) sat_n += !(fabsf(v) <= 65504.f / p.out.a_scale) ? 1 : 0;
+      ring[off] = hi;
+      ring[off + MQ * 32] = lo;
+    });
+    __syncthreads();
+#pragma unroll
+    for (int cb = CB0; cb < CB1; ++cb) {
+      const _Float16* sl = ring + (cb % NSLOT) * SLOT_HALFS;
+      const int st = cb & 1;
+      block_step(acc, sl, sl + MQ * 32, bq[st], l15, phys);
+      __builtin_amdgcn_sched_barrier(0);
+      if (cb + 2 < NCB) load_weights(bq[st], p.wpk, cb + 2, wave, lane);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();         // the next level overwrites the footprints and the consumed ring slots
+  };
+  level(Int<0>{}, Int<0>{}, Int<2>{});          // channels   0 ..  80: blocks 0, 1 complete (block 2 up to channel 80)
+  level(Int<1>{}, Int<2>{}, Int<5>{});          // channels  81 .. 161: blocks 2, 3, 4
+  level(Int<2>{}, Int<5>{}, Int<7>{});          // channels 162 .. 242: blocks 5, 6
+  level(Int<3>{}, Int<7>{}, Int<NCB>{});        // channels 243 .. 323: blocks 7 .. 10
+  if (p.out.sat && sat_n) atomicAdd(p.out.sat, static_cast<unsigned long long>(sat_n));
+
+  // ---- epilogue through an LDS tile aliasing ring + footprints (the last barrier above has passed)
+  tile_epilogue(p.out, acc, reinterpret_cast<float*>(lds), m0, tid);
 }
 
 }  // namespace
@@ -240,31 +161,14 @@ extern "C" int rnnpose_corr_lookup_convc1_f16x3(const float* pyramid, const floa
   const char* fn = "rnnpose_corr_lookup_convc1_f16x3";
   RP_REQUIRE(pyramid && coords && w_packed && bias && dst, fn, "null pointer");
   RP_REQUIRE(levels == 4 && radius == R, fn, "4 pyramid levels, radius 4 (324 window features = the c_in the weights were packed for)");
-  RP_REQUIRE(b0 >= 0 && b0 < b1 && b1 <= B_total, fn, "image range must satisfy 0 <= b0 < b1 <= B");
-  if (dst_split) RP_REQUIRE(dst_c_stride % 8 == 0 && reinterpret_cast<uintptr_t>(dst) % 32 == 0, fn, "split-form dst: channel stride multiple of 8, 32-byte aligned");
-  RP_REQUIRE(dst_c_offset >= 0 && dst_c_offset + 256 <= dst_c_stride && dst_c_offset % 4 == 0 && dst_c_stride % 4 == 0 &&
-                 reinterpret_cast<uintptr_t>(dst) % 16 == 0 && reinterpret_cast<uintptr_t>(w_packed) % 16 == 0, fn,
-             "the 256 output channels must lie inside the row, 16-byte aligned");
-  RP_REQUIRE(a_scale > 0.f && w_scale > 0.f, fn, "scales must be positive");
-  int64_t offs[RNNPOSE_MAX_LEVELS + 1];
   CParams p{};
-  if (int e = rnnpose_corr_pyramid_layout(B_total, h, w, levels, offs, p.info.hl, p.info.wl)) return e;
-  p.info.n_px = rp::cdiv(w, 16);
-  p.info.n_patch = rp::cdiv(h, 8) * p.info.n_px;
-  for (int l = 0; l < levels; ++l) {
-    p.info.off[l] = offs[l];
-    RP_REQUIRE(p.info.hl[l] >= 2 && p.info.wl[l] >= 2, fn, "every pyramid level must be at least 2x2");
-  }
+  if (int e = lookup_info(fn, B_total, b0, b1, h, w, levels, p.info)) return e;
+  if (int e = check_tile_out(fn, dst, dst_c_stride, dst_c_offset, dst_split, a_scale, w_scale, w_packed)) return e;
   const long long n_pixels = static_cast<long long>(b1 - b0) * h * w;
   RP_REQUIRE(n_pixels < (1LL << 31), fn, "bad pixel count");
   p.pyr = pyramid; p.coords = coords; p.N = h * w; p.p_off = static_cast<long long>(b0) * h * w;
   p.wpk = static_cast<const uint4*>(w_packed);
-  p.bias = bias;
-  p.a_scale = a_scale; p.out_scale = 1.0f / (a_scale * w_scale);
-  p.dst = dst; p.dcs = dst_c_stride; p.dco = dst_c_offset; p.relu = relu;
-  p.M = n_pixels;
-  p.sat = rp::sat_counter();
-  p.dst_hl = dst_split;
+  p.out = tile_out(bias, a_scale, w_scale, relu, dst, dst_c_stride, dst_c_offset, dst_split, n_pixels);
   const dim3 grid(static_cast<unsigned>(rp::cdiv(n_pixels, MQ))), block(8 * MQ);
   hipLaunchKernelGGL(corr_convc1_kernel, grid, block, 0, rp::as_stream(stream), p);
   return rp::check_launch(fn);

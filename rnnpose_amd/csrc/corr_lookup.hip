@@ -14,9 +14,7 @@
 // One wave per workgroup (one pyramid level x 16 pixels), 6.5 KB LDS.  The gather is latency-bound: r01 ablation =
 // 0.075 of 0.11 ms in the footprint loads; 64 pixels per wave (25.9 KB LDS, 6 waves per CU) ran at 0.111 ms, 32 at
 // 0.067, 16 at 0.057 (16 waves per CU, the VGPR limit) -- phase 2 then only uses 16 lanes, but it is 5 % of the time.
-#define RP_CONTRACT_LOCAL 1      // (geometry.cuh / induced.cuh: no fma contraction inside THEIR functions only)
 #include "corr_lookup.cuh"
-#include "induced.cuh"
 
 namespace {
 
@@ -31,66 +29,25 @@ __global__ __launch_bounds__(64) void corr_lookup_kernel(const float* __restrict
   const long long total = static_cast<long long>(B) * N;
   const int lane = threadIdx.x;
   const int lvl = blockIdx.y;
-  const long long p = static_cast<long long>(blockIdx.x) * PIX + lane;   // flat (b, Y, X)
+  const long long first = static_cast<long long>(blockIdx.x) * PIX;
+  const long long p = first + lane;                                       // flat (b, Y, X)
   const bool live = lane < PIX && p < total;
-  const int hl = info.hl[lvl], wl = info.wl[lvl];
-  const float inv = 1.0f / static_cast<float>(1 << lvl);
-
-  float cx = 0.f, cy = 0.f;
-  int b = 0, pix = 0;
-  // row of this lane's pixel in the pyramid (image of the WHOLE batch the pyramid was built for, pixel inside it)
-  const long long prow = p_off + (p < total ? p : total - 1);
-  const int bg = static_cast<int>(prow / N), pixg = static_cast<int>(prow - static_cast<long long>(bg) * N);
-  if (live) {
-    b = static_cast<int>(p / N);
-    pix = static_cast<int>(p - static_cast<long long>(b) * N);
-    if (isrc.depth) {
-      // r06: the pose-induced coordinates are formed HERE (induced.cuh: the very function of induced_coords_lowres_kernel) instead of being
-      // read from the output of a launch of their own; the level-0 workgroup of a pixel writes them out for the later consumers
-      const int Y = pix / w, X = pix - Y * w;
-      const float2 c = rp::induced_coords_at(isrc.depth + static_cast<long long>(b) * isrc.H * isrc.W, X, Y, isrc.H, isrc.W, h, w, isrc.eps,
-                                             rp::load_intr(isrc.K, b), rp::load_pose(isrc.G, b));
-      if (lvl == 0 && coords_out) {
-        coords_out[(static_cast<long long>(b) * 2 + 0) * N + pix] = c.x;
-        coords_out[(static_cast<long long>(b) * 2 + 1) * N + pix] = c.y;
-      }
-      cx = c.x * inv;
-      cy = c.y * inv;
-    } else {
-      cx = coords[(static_cast<long long>(b) * 2 + 0) * N + pix] * inv;
-      cy = coords[(static_cast<long long>(b) * 2 + 1) * N + pix] * inv;
-    }
-  }
+  const Centre c = lookup_centre(coords, isrc, coords_out, true, p, total, live, h, w, p_off, lvl);
   int bx, by;
   float ax, ay;
-  footprint_base(cx, cy, bx, by, ax, ay);
+  footprint_base(c.cx, c.cy, bx, by, ax, ay);
 
   // ---- phase 1: cooperative footprint fetch (corr_lookup.cuh) ----
-  const long long first = static_cast<long long>(blockIdx.x) * PIX;
   const int npix = static_cast<int>(total - first < PIX ? total - first : PIX);
-  gather16(pyr, info, lvl, N, lane, npix, bx, by, bg, pixg, p_off + first, foot);
+  gather_batches<PIX>(AddrSelect{wave_maps(pyr, info, lvl, N, c.bg, c.pixg, p_off + first)}, lane, npix, bx, by, foot);
   __syncthreads();
-  // ---- phase 2: lane = pixel ----
-  const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay, w11 = ax * ay;
-  const float* f = foot + (lane < PIX ? lane : 0) * FS;      // (lanes >= PIX idle through phase 2)
+  // ---- phase 2: lane = pixel; y offset j - 4 -> footprint rows j, j + 1; x offset i - 4 -> footprint cols i, i + 1; channel i * 9 + j ----
   float res[WIN * WIN];
-  float prev[FP], cur[FP];
-#pragma unroll
-  for (int x = 0; x < FP; ++x) prev[x] = f[x];
-#pragma unroll
-  for (int j = 0; j < WIN; ++j) {          // y offset j-4  -> footprint rows j, j+1
-#pragma unroll
-    for (int x = 0; x < FP; ++x) cur[x] = f[(j + 1) * FP + x];
-#pragma unroll
-    for (int i = 0; i < WIN; ++i)          // x offset i-4  -> footprint cols i, i+1 ; channel i*9 + j
-      res[i * WIN + j] = w00 * prev[i] + w10 * prev[i + 1] + w01 * cur[i] + w11 * cur[i + 1];
-#pragma unroll
-    for (int x = 0; x < FP; ++x) prev[x] = cur[x];
-  }
+  window_taps<WIN>(foot + (lane < PIX ? lane : 0) * FS, ax, ay, WIN, [&](int i, int j, float v) { res[i * WIN + j] = v; });   // (lanes >= PIX idle through phase 2)
   if (!nhwc) {
     // (B, L*81, h, w): consecutive lanes are consecutive pixels -> one coalesced 256-byte row per channel
     if (live) {
-      float* o = out + (static_cast<long long>(b) * levels * (WIN * WIN) + static_cast<long long>(lvl) * (WIN * WIN)) * N + pix;
+      float* o = out + (static_cast<long long>(c.b) * levels * (WIN * WIN) + static_cast<long long>(lvl) * (WIN * WIN)) * N + c.pix;
 #pragma unroll
       for (int c = 0; c < WIN * WIN; ++c) o[static_cast<long long>(c) * N] = res[c];
     }
@@ -103,22 +60,17 @@ __global__ __launch_bounds__(64) void corr_lookup_kernel(const float* __restrict
       for (int c = 0; c < WIN * WIN; ++c) foot[lane * (WIN * WIN) + c] = res[c];
     }
     __syncthreads();
-    const int ctot = levels * WIN * WIN;
-    float* o = out + first * ctot + lvl * (WIN * WIN);
-    for (int q = 0; q < npix; ++q) {
-      o[static_cast<long long>(q) * ctot + lane] = foot[q * (WIN * WIN) + lane];
-      if (lane < WIN * WIN - 64) o[static_cast<long long>(q) * ctot + 64 + lane] = foot[q * (WIN * WIN) + 64 + lane];
-    }
+    store_rows_nhwc(out, foot, first, npix, levels, lvl, lane);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // r06: the same lookup at half the instructions per wave (RPL_V2 = 1, default; 0 keeps the r01-r05 kernel above for A/B).  The kernel is
 // bound by instructions, not by HBM (98 MB per half-batch launch in 26 us) -- ~1600 per wave for 16 pixels of one level:
-//   * phase 1 by gather_px_fast (corr_lookup.cuh): one address form per level class, scalar pixel bases, 32-bit byte offsets;
+//   * phase 1 with the AddrFast policy (corr_lookup.cuh): one address form per level class, scalar pixel bases, 32-bit byte offsets;
 //   * every lane carries the coordinates of pixel (lane & 15), so that phase 2 runs on 48 lanes instead of 16: lane (q, part) slides the
 //     two-row window over footprint rows 3 part .. 3 part + 3 and produces the 27 channels i * 9 + j, j in [3 part, 3 part + 3) -- the
-//     same expression per channel, bit-identical values -- and writes them into the transposition buffer itself;
+//     same expression per channel (window_taps), bit-identical values -- and writes them into the transposition buffer itself;
 //   * the NHWC rows leave as before (a pixel's 81 values of the level = one contiguous 324-byte run).
 template <bool L0>
 __device__ __forceinline__ void lookup_body_v2(const float* __restrict__ pyr, const float* __restrict__ coords, float* __restrict__ out, int B,
@@ -131,58 +83,19 @@ __device__ __forceinline__ void lookup_body_v2(const float* __restrict__ pyr, co
   const long long first = static_cast<long long>(blockIdx.x) * PIX;
   const long long p = first + q16;                                        // flat (b, Y, X) of this lane's pixel
   const bool live = p < total;
-  const float inv = 1.0f / static_cast<float>(1 << lvl);
-
-  float cx = 0.f, cy = 0.f;
-  int b = 0, pix = 0;
-  const long long prow = p_off + (p < total ? p : total - 1);
-  const int bg = static_cast<int>(prow / N), pixg = static_cast<int>(prow - static_cast<long long>(bg) * N);
-  if (live) {
-    b = static_cast<int>(p / N);
-    pix = static_cast<int>(p - static_cast<long long>(b) * N);
-    if (isrc.depth) {
-      const int Y = pix / w, X = pix - Y * w;
-      const float2 c = rp::induced_coords_at(isrc.depth + static_cast<long long>(b) * isrc.H * isrc.W, X, Y, isrc.H, isrc.W, h, w, isrc.eps,
-                                             rp::load_intr(isrc.K, b), rp::load_pose(isrc.G, b));
-      if (lvl == 0 && coords_out && part == 0) {
-        coords_out[(static_cast<long long>(b) * 2 + 0) * N + pix] = c.x;
-        coords_out[(static_cast<long long>(b) * 2 + 1) * N + pix] = c.y;
-      }
-      cx = c.x * inv;
-      cy = c.y * inv;
-    } else {
-      cx = coords[(static_cast<long long>(b) * 2 + 0) * N + pix] * inv;
-      cy = coords[(static_cast<long long>(b) * 2 + 1) * N + pix] * inv;
-    }
-  }
+  const Centre c = lookup_centre(coords, isrc, coords_out, part == 0, p, total, live, h, w, p_off, lvl);
   int bx, by;
   float ax, ay;
-  footprint_base(cx, cy, bx, by, ax, ay);
+  footprint_base(c.cx, c.cy, bx, by, ax, ay);
 
   // ---- phase 1: cooperative footprint fetch ----
   const int npix = static_cast<int>(total - first < PIX ? total - first : PIX);
-  gather_px_fast<PIX, L0>(pyr, info, lvl, N, lane, npix, bx, by, bg, pixg, p_off + first, foot);
+  gather_batches<PIX>(AddrFast<L0>{wave_maps(pyr, info, lvl, N, c.bg, c.pixg, p_off + first)}, lane, npix, bx, by, foot);
   __syncthreads();
-  // ---- phase 2: lane = (pixel, third of the window rows) ----
-  const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay, w11 = ax * ay;
+  // ---- phase 2: lane = (pixel, third of the window rows): y offset 3 part + jj - 4 -> footprint rows 3 part + jj, + 1 ----
   const int pr = part < 3 ? part : 2;                                     // (the fourth lane group repeats the third one's work and writes nothing)
-  const float* f = foot + q16 * FS + 3 * pr * FP;
   float res[3][WIN];
-  {
-    float prev[FP], cur[FP];
-#pragma unroll
-    for (int x = 0; x < FP; ++x) prev[x] = f[x];
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {         // y offset 3 part + jj - 4 -> footprint rows 3 part + jj, + 1
-#pragma unroll
-      for (int x = 0; x < FP; ++x) cur[x] = f[(jj + 1) * FP + x];
-#pragma unroll
-      for (int i = 0; i < WIN; ++i)          // x offset i - 4 -> footprint cols i, i + 1; channel i * 9 + j
-        res[jj][i] = w00 * prev[i] + w10 * prev[i + 1] + w01 * cur[i] + w11 * cur[i + 1];
-#pragma unroll
-      for (int x = 0; x < FP; ++x) prev[x] = cur[x];
-    }
-  }
+  window_taps<3>(foot + q16 * FS + 3 * pr * FP, ax, ay, 3, [&](int i, int jj, float v) { res[jj][i] = v; });
   __syncthreads();                                                        // every lane is done reading the footprints: the buffer is re-used
   if (part < 3) {
 #pragma unroll
@@ -194,17 +107,12 @@ __device__ __forceinline__ void lookup_body_v2(const float* __restrict__ pyr, co
   if (!nhwc) {
     // (B, L*81, h, w): lanes 0..15 = the 16 pixels; a channel row of 16 consecutive pixels is one 64-byte run
     if (lane < PIX && live) {
-      float* o = out + (static_cast<long long>(b) * levels * (WIN * WIN) + static_cast<long long>(lvl) * (WIN * WIN)) * N + pix;
+      float* o = out + (static_cast<long long>(c.b) * levels * (WIN * WIN) + static_cast<long long>(lvl) * (WIN * WIN)) * N + c.pix;
 #pragma unroll
       for (int c = 0; c < WIN * WIN; ++c) o[static_cast<long long>(c) * N] = foot[lane * (WIN * WIN) + c];
     }
   } else {
-    const int ctot = levels * WIN * WIN;
-    float* o = out + first * ctot + lvl * (WIN * WIN);
-    for (int q = 0; q < npix; ++q) {
-      o[static_cast<long long>(q) * ctot + lane] = foot[q * (WIN * WIN) + lane];
-      if (lane < WIN * WIN - 64) o[static_cast<long long>(q) * ctot + 64 + lane] = foot[q * (WIN * WIN) + 64 + lane];
-    }
+    store_rows_nhwc(out, foot, first, npix, levels, lvl, lane);
   }
 }
 
@@ -237,17 +145,8 @@ static int launch_lookup(const char* fn, const float* pyramid, const float* coor
                          float* coords_out = nullptr) {
   RP_REQUIRE(pyramid && (coords || isrc.depth) && out, fn, "null pointer");
   RP_REQUIRE(radius == R, fn, "radius must be 4");
-  RP_REQUIRE(b0 >= 0 && b0 < b1 && b1 <= B_total, fn, "image range must satisfy 0 <= b0 < b1 <= B");
-  int64_t offs[RNNPOSE_MAX_LEVELS + 1];
   LookupInfo info{};
-  if (int e = rnnpose_corr_pyramid_layout(B_total, h, w, levels, offs, info.hl, info.wl)) return e;
-  info.n_px = rp::cdiv(w, 16);
-  info.n_patch = rp::cdiv(h, 8) * info.n_px;
-  for (int l = 0; l < levels; ++l) {
-    info.off[l] = offs[l];
-    // the reference divides by (W_l - 1): a 1-wide level yields inf/NaN there
-    RP_REQUIRE(info.hl[l] >= 2 && info.wl[l] >= 2, fn, "every pyramid level must be at least 2x2");
-  }
+  if (int e = lookup_info(fn, B_total, b0, b1, h, w, levels, info)) return e;
   const int B = b1 - b0;
   const long long total = static_cast<long long>(B) * h * w;
   dim3 grid(static_cast<unsigned>(rp::cdiv(total, PIX)), static_cast<unsigned>(levels)), block(64);

@@ -88,7 +88,7 @@ SOURCES = ["pointwise.hip", "corr_pyramid.hip", "corr_lookup.hip", "corr_convc1.
 EXTRA = ["runtime_host.cpp"]
 # headers that need no host patch but may be named by HOSTEXEC_MUTATE -> the SOURCES that include them: the mutated header is written
 # next to scratch copies of those sources (quote includes look there first)
-MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"]}
+MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"], "resident_tile.cuh": ["conv1x1_resident.hip", "corr_convc1.hip"]}
 
 
 def clang() -> str:
