@@ -202,6 +202,32 @@ int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const floa
                                 int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
                                 void* workspace, size_t workspace_bytes, double* Hm, double* bv, float* xi, int* info,
                                 double* dstats, rnnpose_stream_t stream);
+/* ---- the grouped step (multi-view): ONE increment per object from the summed systems of all its views.
+ * The B rows of the batch are VIEWS; the views of group g are rows [group_start[g], group_start[g+1]) (group_start: (n_groups+1) int32
+ * device pointer, 0 = group_start[0] < ... < group_start[n_groups] = B).  E (B,4,4) fp32 row-major: the camera-from-rig transform
+ * E_v = (R, t) of every view (a single camera: the identity).  With T_v = E_v T_rig, a rig-frame left increment delta acts in view v as
+ * xi_v = Ad(E_v) delta, Ad(E) = [[R, [t]x R], [0, R]] (translation first).  Per iteration:
+ *  1. Hm (B,6,6), bv (B,6) (and dstats (B,2), with the depth term): every VIEW's undamped system, bit-identical to
+ *     rnnpose_lm_normal_eq_f64 (obs_depth == NULL: the plain sums; theta, K_obs, src_index, S, Ho, Wo, depth_weight, depth_gate, edge_tol
+ *     are then ignored and dstats stays unwritten) or to rnnpose_lm_normal_eq_rgbd_f64 of the same arguments;
+ *  2. Hg (n_groups,6,6) = sum_v Ad_v^T Hm_v Ad_v, bg (n_groups,6) = sum_v Ad_v^T bv_v in fp64, the views in ascending order, no atomics:
+ *     deterministic, Hg exactly symmetric;
+ *  3. xi (n_groups,6), info (n_groups): the damped solve of rnnpose_lm_solve_update_f32 on Hg, bg (same operations, same order);
+ *  4. D = exp(xi) once per group; every view of the group: G_v <- (E_v D E_v^-1) G_v in fp32 (E_v^-1 the rigid inverse).
+ * num_iters >= 1; later iterations continue in place on G_out (which may alias G_in); the outputs hold the LAST iteration's values.
+ * Two launches per iteration (the partial sums, then one workgroup per group); rnnpose_lm_fused_tail does not apply.  The workspace is
+ * that of the other steps (rnnpose_lm_workspace_bytes(B,H,W)) and may be shared with them: no arrival counter is used or left non-zero.
+ * The kernel clamps every range to [0, B]; a group that is empty after that gets info = -1 and nothing else of it is written.  With
+ * every group of one view and E the identity, G_out, Hm, bv, xi, info are those of rnnpose_lm_step_io_f32 / _rgbd_io_f32 bit for bit.
+ * Returns 1 for a null group_start / E / Hg / bg / xi / info, n_groups < 1 or > B, and everything the ungrouped steps refuse. */
+int rnnpose_lm_step_views_io_f32(const float* target, int target_mode, const float* weight, const float* depth,
+                                 float depth_eps, const float* K, const float* G_in, float* G_out, int B, int H, int W,
+                                 int num_iters, double ep_lambda, double lm_lambda, double max_update,
+                                 const float* obs_depth, const int* src_index, const float* theta, const float* K_obs,
+                                 int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
+                                 const int* group_start, int n_groups, const float* E,
+                                 void* workspace, size_t workspace_bytes, double* Hm, double* bv, double* Hg, double* bg,
+                                 float* xi, int* info, double* dstats, rnnpose_stream_t stream);
 /* The fused steps run ONE launch per Gauss-Newton iteration: the workgroup that arrives last for an image (device-scope ticket
  * in the workspace, which must therefore be ZERO-FILLED when it is allocated) sums the partial records, solves and updates the
  * pose.  rnnpose_lm_fused_tail(0) restores the three-launch form (normal equations, finalize, solve) for measurements. */

@@ -69,6 +69,8 @@ PROTOTYPES = {
     "rnnpose_lm_normal_eq_rgbd_f64": (_i, [_p, _i, _p, _p, _f, _p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p, _z, _p, _p, _p, _p]),
     "rnnpose_lm_step_rgbd_io_f32": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _d, _d, _d, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f,
                                          _p, _z, _p, _p, _p, _p, _p, _p]),
+    "rnnpose_lm_step_views_io_f32": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _d, _d, _d, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f,
+                                          _p, _i, _p, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rnnpose_lm_fused_tail": (_i, [_i]),
     "rnnpose_se3_exp_f32": (_i, [_p, _i, _p, _p]),
     "rnnpose_se3_compose_f32": (_i, [_p, _p, _i, _p, _p]),

@@ -503,9 +503,9 @@ __device__ void mat4_mul(const float* A, const float* Bm, float* C) {
     }
 }
 
-// damping, 6x6 Cholesky solve, NaN -> 0, clamp, SE(3) exponential and left increment of image b (one thread)
-__device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv, const float* G, int b, double ep, double lm,
-                                             double max_update, float* G_new /* may alias G */, float* xi_out, int* info) {
+// damping, 6x6 Cholesky solve, NaN -> 0, clamp of system b -> xi (and xi_out, info) (one thread)
+__device__ __forceinline__ void lm_solve_xi(const double* Hm, const double* bv, int b, double ep, double lm, double max_update, float (&xi)[6],
+                                            float* xi_out, int* info) {
   // (the fused tail reads H, b that this very thread's block wrote a barrier ago: same CU, same L1 -- plain loads are current)
   // In place on the lower triangle (21 doubles instead of two 6x6 arrays: this function's registers are the floor of every kernel
   // that calls it, r04) -- the same operations in the same order as the two-array form.
@@ -555,7 +555,6 @@ __device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv,
     xv[i] = t / LT(i, i);
   }
 #undef LT
-  float xi[6];
   for (int i = 0; i < 6; ++i) {
     double v = xv[i];
     if (v != v) v = 0.0;                                   // NaN -> 0      (cholesky.py:43-44)
@@ -564,11 +563,115 @@ __device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv,
     xi_out[b * 6 + i] = xi[i];
   }
   if (info) info[b] = bad;
+}
+
+// SE(3) exponential and left increment of image b: G_new <- exp(xi) G (one thread)
+__device__ __forceinline__ void lm_pose_update(const float (&xi)[6], const float* G, int b, float* G_new /* may alias G */) {
   float dG[16], Gin[16], Gout[16];
   se3_exp_dev(xi, dG);
   for (int i = 0; i < 16; ++i) Gin[i] = G[b * 16 + i];
   mat4_mul(dG, Gin, Gout);                                 // se3.py:303-306
   for (int i = 0; i < 16; ++i) G_new[b * 16 + i] = Gout[i];
+}
+
+// the solve and the pose update of image b (one thread): what every ungrouped LM step ends with
+__device__ __forceinline__ void lm_solve_one(const double* Hm, const double* bv, const float* G, int b, double ep, double lm,
+                                             double max_update, float* G_new /* may alias G */, float* xi_out, int* info) {
+  float xi[6];
+  lm_solve_xi(Hm, bv, b, ep, lm, max_update, xi, xi_out, info);
+  lm_pose_update(xi, G, b, G_new);
+}
+
+// ---- views of one object from several calibrated cameras: ONE increment per group of views ----------------------
+// View v has the camera-from-rig transform E_v = (R, t); a rig-frame left increment delta acts in view v as xi_v = Ad(E_v) delta,
+// Ad(E) = [[R, [t]x R], [0, R]].  Group system Hg = sum_v Ad_v^T Hm_v Ad_v, bg = sum_v Ad_v^T bv_v (fp64, views in ascending order), the
+// solve of every LM step on it, D = exp(delta) once per group, and G_v <- (E_v D E_v^-1) G_v for every view of the group.
+struct LmViews {
+  const int* group_start;       // (n_groups + 1): the views of group g are rows [group_start[g], group_start[g + 1])
+  int n_groups;
+  const float* E;               // (B,4,4) camera-from-rig of every view
+  double* Hg;                   // (n_groups,6,6), (n_groups,6): the undamped rig-frame system
+  double* bg;
+};
+
+// entry (i, j) of Ad(E) in fp64 from the fp32 transform e (16 floats, row-major)
+__device__ __forceinline__ double lm_adjoint_entry(const float* e, int i, int j) {
+  if (i >= 3) return j >= 3 ? static_cast<double>(e[(i - 3) * 4 + (j - 3)]) : 0.0;
+  if (j < 3) return static_cast<double>(e[i * 4 + j]);
+  // ([t]x R)(i, c) = t_{i+1} R(i+2, c) - t_{i+2} R(i+1, c), indices modulo 3
+  const int c = j - 3, i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+  const double t1 = e[i1 * 4 + 3], t2 = e[i2 * 4 + 3];
+  return t1 * static_cast<double>(e[i2 * 4 + c]) - t2 * static_cast<double>(e[i1 * 4 + c]);
+}
+
+// The tail of a grouped iteration behind lm_eq_kernel<., false>: one 256-thread workgroup per group.  Per view: the partial records ->
+// Hm_v, bv_v (dstats) by lm_finalize_block_one itself (bit-identical to the ungrouped entries), then Ad_v^T Hm_v Ad_v (36 threads, every
+// one the entry (min, max) of its pair: Hg is exactly symmetric) and Ad_v^T bv_v (6 threads) added to per-thread fp64 accumulators in
+// ascending view order -- no atomics, deterministic.  One thread damps, solves and clamps (lm_solve_xi: the solve of every LM step) and
+// forms D; the views of the group then update their poses in parallel.  Ranges are clamped to [0, B]; an empty group writes info = -1
+// and nothing else.  tail: Hm, bv, dstats, G_in, G_out per VIEW, xi and info per GROUP; no tickets are used.
+__global__ __launch_bounds__(256) void lm_views_tail_kernel(const double* __restrict__ partials, int nblk, int B, const LmViews vw,
+                                                            const LmTail tail) {
+  __shared__ double Ad[36], M[36];
+  __shared__ float Dg[16];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const int v0 = min(max(vw.group_start[g], 0), B), v1 = min(max(vw.group_start[g + 1], 0), B);
+  if (v1 <= v0) {
+    if (tid == 0) tail.info[g] = -1;
+    return;
+  }
+  const int i = tid < 36 ? tid / 6 : 0, j = tid < 36 ? tid % 6 : tid - 36;
+  const int r = i < j ? i : j, c = i < j ? j : i;
+  double acc = 0.0;
+  for (int v = v0; v < v1; ++v) {
+    lm_finalize_block_one(partials, nblk, v, tail.Hm, tail.bv, tail.dstats);   // (ends with the values in global memory, written by this block)
+    if (tid < 36) Ad[tid] = lm_adjoint_entry(vw.E + v * 16, i, j);
+    __syncthreads();
+    if (tid < 36) {                                                            // M = Hm_v Ad_v
+      double s = 0.0;
+      for (int k = 0; k < 6; ++k) s += tail.Hm[v * 36 + i * 6 + k] * Ad[k * 6 + j];
+      M[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 36) {
+      double s = 0.0;
+      for (int k = 0; k < 6; ++k) s += Ad[k * 6 + r] * M[k * 6 + c];
+      acc += s;
+    } else if (tid < 42) {
+      double s = 0.0;
+      for (int k = 0; k < 6; ++k) s += Ad[k * 6 + j] * tail.bv[v * 6 + k];
+      acc += s;
+    }
+    __syncthreads();                                                           // (the next view overwrites Ad and M)
+  }
+  if (tid < 36) vw.Hg[g * 36 + tid] = acc;
+  else if (tid < 42) vw.bg[g * 6 + j] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    float xi[6];
+    lm_solve_xi(vw.Hg, vw.bg, g, tail.ep, tail.lm, tail.max_update, xi, tail.xi, tail.info);
+    se3_exp_dev(xi, Dg);
+  }
+  __syncthreads();
+  for (int v = v0 + tid; v < v1; v += blockDim.x) {                            // G_v <- (E_v D E_v^-1) G_v, fp32
+    float e[16], d[16], inv[16], a[16], m[16], Gin[16], Gout[16];
+    for (int q = 0; q < 16; ++q) {
+      e[q] = vw.E[v * 16 + q];
+      d[q] = Dg[q];
+      Gin[q] = tail.G_in[v * 16 + q];
+    }
+    for (int p = 0; p < 3; ++p) {                                              // the rigid inverse, as se3_inverse_kernel forms it
+      for (int q = 0; q < 3; ++q) inv[p * 4 + q] = e[q * 4 + p];
+      float s = 0.f;
+      for (int k = 0; k < 3; ++k) s += e[k * 4 + p] * e[k * 4 + 3];
+      inv[p * 4 + 3] = -s;
+    }
+    inv[12] = 0.f; inv[13] = 0.f; inv[14] = 0.f; inv[15] = 1.f;
+    mat4_mul(e, d, a);
+    mat4_mul(a, inv, m);
+    mat4_mul(m, Gin, Gout);
+    for (int q = 0; q < 16; ++q) tail.G_out[v * 16 + q] = Gout[q];
+  }
 }
 
 __global__ __launch_bounds__(64) void lm_solve_update_kernel(const double* __restrict__ Hm, const double* __restrict__ bv,
@@ -684,7 +787,13 @@ int launch_lm_eq(const LmInputs& in, const LmDepthTerm* dt, const LmTail& tail, 
 
 // ONE LM iteration.  fused: partial sums + (in the last-arriving workgroup of every image) finalize, damped solve, pose update as ONE
 // launch; else partial sums, finalize (with the statistics, given tail.dstats) and -- given tail.G_out -- the solve as three launches
-void launch_lm_iteration(bool fused, const LmInputs& in, const LmDepthTerm* dt, const LmTail& tail, hipStream_t st) {
+// views: the grouped step -- partial sums, then lm_views_tail_kernel (finalize per view, group system, solve, pose updates): two launches
+void launch_lm_iteration(bool fused, const LmInputs& in, const LmDepthTerm* dt, const LmTail& tail, const LmViews* views, hipStream_t st) {
+  if (views) {
+    const int nblk = launch_lm_eq<false>(in, dt, tail, st);
+    hipLaunchKernelGGL(lm_views_tail_kernel, dim3(views->n_groups), dim3(256), 0, st, lm_partials(in.workspace, in.B), nblk, in.B, *views, tail);
+    return;
+  }
   if (fused) {
     launch_lm_eq<true>(in, dt, tail, st);
     return;
@@ -754,14 +863,18 @@ static int lm_check(const char* fn, const LmInputs& in, const LmDepthTerm* dt, c
   return 0;
 }
 
-// every LM entry: the checks, then num_iters iterations from G_in in the form that g_lm_fused and the presence of `info` select
+// every LM entry: the checks, then num_iters iterations from G_in in the form that g_lm_fused and the presence of `info` select;
+// views: the grouped step's arguments (tested first, the group count once the batch size is known to be good), or null
 static int lm_run(const char* fn, const LmInputs& in, const LmDepthTerm* dt, const float* G_in, LmTail tail, bool solve, int num_iters,
-                  bool need_iter, rnnpose_stream_t stream) {
+                  bool need_iter, rnnpose_stream_t stream, const LmViews* views = nullptr) {
+  if (views) RP_REQUIRE(views->group_start && views->E && views->Hg && views->bg && tail.xi && tail.info, fn,
+                        "null group_start / E / Hg / bg / xi / info");
   if (lm_check(fn, in, dt, G_in, tail, solve, num_iters, need_iter)) return 1;
+  if (views) RP_REQUIRE(views->n_groups >= 1 && views->n_groups <= in.B, fn, "n_groups must lie in [1, B]");
   hipStream_t st = rp::as_stream(stream);
   for (int it = 0; it < num_iters; ++it) {
     tail.G_in = it == 0 ? G_in : tail.G_out;              // later iterations continue in place on the output
-    launch_lm_iteration(g_lm_fused && tail.info, in, dt, tail, st);
+    launch_lm_iteration(g_lm_fused && tail.info, in, dt, tail, views, st);
   }
   return rp::check_launch(fn);
 }
@@ -814,6 +927,21 @@ int rnnpose_lm_step_rgbd_io_f32(const float* target, int target_mode, const floa
   const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
   return lm_run("rnnpose_lm_step_rgbd_io_f32", in, &dt, G_in, lm_tail(workspace, Hm, bv, G_out, xi, info, ep_lambda, lm_lambda, max_update, dstats),
                 true, num_iters, true, stream);
+}
+
+int rnnpose_lm_step_views_io_f32(const float* target, int target_mode, const float* weight, const float* depth, float depth_eps,
+                                 const float* K, const float* G_in, float* G_out, int B, int H, int W, int num_iters, double ep_lambda,
+                                 double lm_lambda, double max_update, const float* obs_depth, const int* src_index, const float* theta,
+                                 const float* K_obs, int S, int Ho, int Wo, float depth_weight, float depth_gate, float edge_tol,
+                                 const int* group_start, int n_groups, const float* E, void* workspace, size_t workspace_bytes, double* Hm,
+                                 double* bv, double* Hg, double* bg, float* xi, int* info, double* dstats, rnnpose_stream_t stream) {
+  const LmInputs in{target, target_mode, weight, depth, depth_eps, K, B, H, W, workspace, workspace_bytes};
+  const LmDepthTerm dt{obs_depth, src_index, theta, K_obs, S, Ho, Wo, depth_weight, depth_gate, edge_tol};
+  const LmViews views{group_start, n_groups, E, Hg, bg};
+  // (the plain kernel never writes the statistics' slots of its records: without the depth term dstats stays unwritten)
+  return lm_run("rnnpose_lm_step_views_io_f32", in, obs_depth ? &dt : nullptr, G_in,
+                lm_tail(workspace, Hm, bv, G_out, xi, info, ep_lambda, lm_lambda, max_update, obs_depth ? dstats : nullptr), true, num_iters, true,
+                stream, &views);
 }
 
 int rnnpose_se3_exp_f32(const float* xi, int B, float* out, rnnpose_stream_t stream) {

@@ -210,19 +210,25 @@ class UpdateEngine:
 
     MIN_CHAIN_PIXELS = 8192     # 1/8-resolution pixels per chain below which the batch stays ONE chain
 
-    def halves(self, B):
+    def halves(self, B, cuts=None):
         """Image ranges of the concurrent chains: `parts` parts of the batch (one stream each), or the whole batch.
         A chain needs enough pixels to fill the chip on its own launches: B=16 at 240x240 (14400 pixels at 1/8 resolution) runs
         3 % faster as one chain than as two of 7200 (1009 vs 978 iters/s), B=32 (two of 14400) 3 % faster as two, the headline
         shape (two of 19200) 5 % faster as two (r02) -- on the 128-row kernels; with the strip kernels (r04-r05): 2-3.5 % at the
-        headline.  RNNPOSE_SPLIT_BATCH=0: always one chain; RNNPOSE_PARTS=n: exactly n (see __init__)."""
+        headline.  RNNPOSE_SPLIT_BATCH=0: always one chain; RNNPOSE_PARTS=n: exactly n (see __init__).
+        cuts: the rows at which the batch MAY be cut (the group starts of ops.ViewGroups: the views of one object stay in one chain);
+        every cut moves to the nearest of them (the lower one on a tie), empty parts are dropped, and without an interior boundary
+        left there is one chain."""
         n = 1 if (B < 2 or not (self.split_batch or self.parts_forced)) else min(self.parts, B)
         if n > 1 and not self.parts_forced and self._buf_key is not None:
             _, h, w, _ = self._buf_key
             while n > 1 and B * h * w < n * self.MIN_CHAIN_PIXELS:
                 n -= 1
-        cuts = [B * i // n for i in range(n + 1)]
-        return list(zip(cuts[:-1], cuts[1:]))
+        rows = [B * i // n for i in range(n + 1)]
+        if cuts is not None and n > 1:
+            allowed = sorted({int(c) for c in cuts if 0 <= int(c) <= B} | {0, B})
+            rows = sorted({0, B} | {min(allowed, key=lambda a: (abs(a - r), a)) for r in rows[1:-1]})
+        return list(zip(rows[:-1], rows[1:]))
 
     def half_gen(self, corr_fn, coords1_part, B, b0, b1, st, flow_up_part, single=False, induced=None):
         """One GRU step of images [b0, b1) on stream `st` (current): window lookup -> update block -> convex up-sampling.

@@ -56,6 +56,8 @@ class EvalItem:
     geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image (None: HipEpoch(desc2d=...) computes them)
     frame_id: int | None = None  # camera frame the object was seen in: items of one frame share `image` / `geofea_2d` (None: its own)
     depth: torch.Tensor | None = None   # (H,W) observed depth of the frame in the meshes' unit, 0 = missing; shared like `image` (BOP VSD)
+    object_id: object = None     # views of ONE physical object from several calibrated cameras share it (None: the item is its own object)
+    cam_from_rig: np.ndarray | None = None   # (4,4) camera-from-rig transform of the item's camera (None: the identity)
 
 
 class PackedEpochMetrics:
@@ -201,6 +203,8 @@ class HipEpoch:
             PoseRefiner(self.cfg, renderer=self.renderer, occlusion=occlusion, occlusion_margin=occlusion_margin,
                         depth_term=depth_term).to(self.device).eval()
         self.last_depth_stats = None
+        self.last_rig_poses = None        # refine_frame with multi-view items: T_rig (n_groups,4,4) of the last call, groups in order of first appearance
+        self._view_groups = {}            # ops.ViewGroups by (layout, transforms): the same rig keeps its device arrays, so captured graphs replay
         self.symmetric = tuple(symmetric)
         # desc2d: a descriptor2d.SuperPoint2D -- items without geofea_2d get theirs from the batch image on the device, as
         # model/RNNPose.py:162 computes them (HybridNet.py:97 keeps the descriptors only)
@@ -261,9 +265,29 @@ class HipEpoch:
         """The objects of one or several camera frames, of any classes, in ONE PoseRefiner call: the image and its descriptor
         map are held once per distinct frame (items with the same non-None frame_id; an item without one is its own frame),
         `SuperPoint2D.descriptors` runs once per frame that carries no geofea_2d, and every object crops its frame through
-        image_index.  -> (B,4,4) refined poses in batch order."""
+        image_index.  -> (B,4,4) refined poses in batch order.
+        Multi-view: items with the same non-None `object_id` are views of one object from cameras with the
+        camera-from-rig transforms `cam_from_rig`; they are refined as one group (PoseRefiner.forward(view_groups=)): one increment per
+        object, the poses tied by the rig.  The pose_init of a group's FIRST item (in batch order) is its start, the others' are
+        ignored.  Items without object_id are groups of one.  `last_rig_poses` then holds T_rig per group."""
         from .transformation import SE3Sequence
         dev = self.device
+        order = vgroups = None
+        if any(it.object_id is not None or it.cam_from_rig is not None for it in batch):
+            from . import ops
+            gid = {}
+            for j, it in enumerate(batch):
+                gid.setdefault(("obj", it.object_id) if it.object_id is not None else ("item", j), len(gid))
+            gof = [gid[("obj", it.object_id) if it.object_id is not None else ("item", j)] for j, it in enumerate(batch)]
+            order = sorted(range(len(batch)), key=lambda j: (gof[j], j))          # groups contiguous, first appearance first
+            batch = [batch[j] for j in order]
+            E = np.stack([np.eye(4, dtype=np.float32) if it.cam_from_rig is None else np.asarray(it.cam_from_rig, np.float32) for it in batch])
+            key = (tuple(gof[j] for j in order), E.tobytes())
+            vgroups = self._view_groups.get(key)
+            if vgroups is None:
+                if len(self._view_groups) >= 8:
+                    self._view_groups.pop(next(iter(self._view_groups)))
+                vgroups = self._view_groups[key] = ops.ViewGroups(key[0], E, len(batch), dev)
         src, index = {}, []
         for j, it in enumerate(batch):
             key = ("frame", it.frame_id) if it.frame_id is not None else ("item", j)
@@ -284,9 +308,18 @@ class HipEpoch:
             fea = [self.models[n].fea_3d.to(dev)[0] for n in names]
             geo = [self.models[n].geofea_3d.to(dev)[0] for n in names]
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=fea, Tj_gt=SE3Sequence(matrix=Tg[:, None]),
-                           obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index, **self._observed_depth(firsts))
+                           obj_cls=names, geofea_3d=geo, geofea_2d=g2, image_index=index, **self._observed_depth(firsts),
+                           **({} if vgroups is None else dict(view_groups=vgroups)))
         self.last_depth_stats = out.get("depth_stats")
-        return out["Ti_pred"].G.reshape(-1, 4, 4)
+        self.last_rig_poses = out.get("T_rig")
+        poses = out["Ti_pred"].G.reshape(-1, 4, 4)
+        if order is None:
+            return poses
+        back = torch.empty(len(order), dtype=torch.long)
+        back[torch.tensor(order)] = torch.arange(len(order))                      # the caller's order
+        if self.last_depth_stats is not None:
+            self.last_depth_stats = self.last_depth_stats[back.to(dev)]
+        return poses[back.to(dev)]
 
     def bop_metrics(self, batch, pose_pred, want_errors=False):
         """BOP recalls of the poses `pose_pred` (B,4,4) of the items of `batch` (any classes, one or several camera frames):
@@ -402,13 +435,16 @@ def synthetic_dataset(models, n_items, image_size=(480, 640), seed=0, pose_sigma
 
 
 def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640), seed=0, pose_sigma=(0.05, 0.01), renderer=None,
-                     device="cuda"):
+                     device="cuda", cameras=None):
     """n_frames camera frames with objects_per_frame objects each, of different classes (cycling through them), at separated
     image positions and depths: every object is rendered at its ground-truth pose by `renderer` (MeshRenderer) and the frame is
     composed by nearest depth in torch -- colour and rendered descriptors alike -- so nearer objects occlude farther ones.
     Every object becomes an EvalItem that SHARES the frame's image and geofea_2d tensors and carries its frame_id; items of a
     frame are consecutive, and `depth`, the composed nearest depth (0 on the background): the frame's observed depth for the BOP VSD.
-    renderer=None (CPU): hash noise per frame instead of a render, and no depth."""
+    renderer=None (CPU): hash noise per frame instead of a render, and no depth.
+    cameras: a list of (4,4) camera-from-rig matrices E_c -- every frame becomes len(cameras) images of the same objects (the poses
+    above are then rig-frame poses): pose_gt = E_c g, frame_id = (f, c), object_id = (f, j), cam_from_rig = E_c, and ONE initial error
+    per object, expressed in the rig frame (pose_init = E_c exp(xi) g).  Items of an image are consecutive, images in camera order."""
     from . import synthetic as syn
     from .evaluator import LINEMOD_K
     H, W = image_size
@@ -420,7 +456,8 @@ def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640),
     # grid cells of 0.8 x the image at 0.8 m, shrunk towards the centre so that the objects stay inside the frame
     dx, dy = 0.8 * W / K[0, 0] * 0.8 / max(cols, 1), 0.8 * H / K[1, 1] * 0.8 / max(rows, 1)
     items = []
-    for f in range(n_frames):
+    cams = [None] if cameras is None else [np.asarray(E, np.float64).reshape(4, 4) for E in cameras]
+    for f, c in ((f, c) for f in range(n_frames) for c in range(len(cams))):
         frame = []
         for j in range(objects_per_frame):
             cls = names[(f + j) % len(names)]
@@ -430,10 +467,15 @@ def synthetic_scenes(models, n_frames, objects_per_frame, image_size=(480, 640),
             g[:3, 3] = syn.uniform(f"st{i}", (3,), seed, -0.1, 0.1) * np.array([dx, dy, 0.05]) + cell      # jitter within the cell
             xi = syn.normal(f"sxi{i}", (1, 6), seed)[0] * np.array([pose_sigma[1]] * 3 + [pose_sigma[0]] * 3)
             init = syn.se3_exp_np(xi[None])[0] @ g
-            frame.append(EvalItem(cls, None, K.copy(), init.astype(np.float32), g.astype(np.float32), None, frame_id=f))
+            if cameras is None:
+                frame.append(EvalItem(cls, None, K.copy(), init.astype(np.float32), g.astype(np.float32), None, frame_id=f))
+            else:
+                frame.append(EvalItem(cls, None, K.copy(), (cams[c] @ init).astype(np.float32), (cams[c] @ g).astype(np.float32), None,
+                                      frame_id=(f, c), object_id=(f, j), cam_from_rig=cams[c].astype(np.float32)))
         if renderer is None:
-            image = torch.from_numpy(syn.uniform(f"simg{f}", (3, H, W), seed) * 255.0)
-            g2 = torch.from_numpy(syn.normal(f"sg2{f}", (32, H, W), seed))
+            tag = f"{f}" if cameras is None else f"{f}c{c}"
+            image = torch.from_numpy(syn.uniform(f"simg{tag}", (3, H, W), seed) * 255.0)
+            g2 = torch.from_numpy(syn.normal(f"sg2{tag}", (32, H, W), seed))
         else:
             dev = torch.device(device)
             Tg = torch.as_tensor(np.stack([it.pose_gt for it in frame])).to(dev)

@@ -566,6 +566,145 @@ def lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_index
     return Gd, Hm, bv, xi, info, dstats
 
 
+# ---- views of one object from several calibrated cameras ---------------------------------------
+class ViewGroups:
+    """Which rows of a batch are views of one object, and every view's camera-from-rig transform (`lm_step_views`,
+    `PoseRefiner.forward(view_groups=)`).  groups: either group_of_view, B group numbers 0, 0, .., 1, 1, .. (starting at 0, every next
+    one equal or one larger: the views of a group are contiguous rows), or group_start, n_groups + 1 row numbers 0 < .. < B (the list
+    whose last entry is B).  cam_from_rig: (B,4,4) rigid transforms E_v (finite, last row 0 0 0 1), or None = the identity for every
+    view.  Checked ON THE HOST once (ValueError); holds the device copies the kernel reads.  Build it once per batch."""
+
+    def __init__(self, groups, cam_from_rig, B, device):
+        B = int(B)
+        if isinstance(groups, torch.Tensor):
+            if groups.dtype.is_floating_point or groups.dtype == torch.bool or groups.dim() != 1:
+                raise ValueError("ViewGroups: groups must be a 1-D integer tensor")
+            groups = groups.detach().cpu().tolist()
+        host = [int(v) for v in groups]
+        if B < 1 or not host:
+            raise ValueError(f"ViewGroups: needs at least one view and one group (B = {B}, {len(host)} entries)")
+        if host[-1] != B:                                               # group_of_view -> group_start
+            if len(host) != B or host[0] != 0 or any(b - a not in (0, 1) for a, b in zip(host, host[1:])):
+                raise ValueError(f"ViewGroups: group_of_view must name {B} views with group numbers that start at 0 and stay or grow by one "
+                                 f"from row to row; got {host[:8]}{'...' if len(host) > 8 else ''}")
+            host = [0] + [i for i in range(1, B) if host[i] != host[i - 1]] + [B]
+        if host[0] != 0 or len(host) < 2 or any(b <= a for a, b in zip(host, host[1:])):
+            raise ValueError(f"ViewGroups: group_start must start at 0, increase strictly and end at B = {B}; got {host[:8]}"
+                             f"{'...' if len(host) > 8 else ''}")
+        if cam_from_rig is None:
+            E = torch.eye(4, dtype=F32).repeat(B, 1, 1)
+        else:
+            E = torch.as_tensor(cam_from_rig).detach().to(device="cpu", dtype=F32).reshape(-1, 4, 4).contiguous()
+            if E.shape[0] != B:
+                raise ValueError(f"ViewGroups: cam_from_rig holds {E.shape[0]} transforms, the batch {B} views")
+            last = torch.tensor([0.0, 0.0, 0.0, 1.0])
+            if not bool(torch.isfinite(E).all()) or not bool((E[:, 3] == last).all()):
+                raise ValueError("ViewGroups: cam_from_rig must be finite with the last row 0 0 0 1")
+        self.B = B
+        self.host = tuple(host)
+        self.E_host = E
+        self.group_start = torch.tensor(host, dtype=torch.int32, device=device)
+        self.E = E.to(device)
+
+    @classmethod
+    def from_device(cls, group_start, E, host, E_host):
+        """Checked groups over other device copies of the same entries (the persistent input buffers of a captured graph)."""
+        self = cls.__new__(cls)
+        self.host, self.E_host, self.group_start, self.E = tuple(host), E_host, group_start, E
+        self.B = self.host[-1]
+        return self
+
+    @property
+    def n_groups(self):
+        return len(self.host) - 1
+
+    def __len__(self):
+        return self.B
+
+    def key(self):
+        """The group layout (what a captured graph depends on besides the buffers)."""
+        return self.host
+
+    def first_rows(self):
+        return self.host[:-1]
+
+    def first_rows_dev(self):
+        """(n_groups,) int64 device tensor: the row of every group's first view"""
+        if getattr(self, "_first_rows", None) is None:
+            self._first_rows = torch.tensor(self.host[:-1], dtype=torch.int64, device=self.E.device)
+        return self._first_rows
+
+    def first_of_view(self):
+        """(B,) int64 device tensor: for every view, the row of its group's first view"""
+        if getattr(self, "_first_of_view", None) is None:
+            rows = [a for a, b in zip(self.host, self.host[1:]) for _ in range(b - a)]
+            self._first_of_view = torch.tensor(rows, dtype=torch.int64, device=self.E.device)
+        return self._first_of_view
+
+    def rows(self, b0, b1):
+        """The groups of rows [b0, b1) as ViewGroups of that batch part; b0 and b1 must be group boundaries (ValueError)."""
+        b0, b1 = int(b0), int(b1)
+        if b0 == 0 and b1 == self.B:
+            return self
+        parts = self.__dict__.setdefault("_parts", {})                  # (memoised: a captured graph reads the part's device array)
+        if (b0, b1) in parts:
+            return parts[(b0, b1)]
+        if b0 not in self.host or b1 not in self.host or not b0 < b1:
+            raise ValueError(f"ViewGroups.rows: [{b0}, {b1}) does not start and end at group boundaries {self.host}")
+        g0, g1 = self.host.index(b0), self.host.index(b1)
+        part = ViewGroups.__new__(ViewGroups)
+        part.B = b1 - b0
+        part.host = tuple(v - b0 for v in self.host[g0:g1 + 1])
+        part.E_host, part.E = self.E_host[b0:b1], self.E[b0:b1]
+        part.group_start = torch.tensor(part.host, dtype=torch.int32, device=self.group_start.device)
+        parts[(b0, b1)] = part
+        return part
+
+
+def lm_step_views(target, weight, depth, K, G, groups, rgbd=None, num_iters=1, ep_lambda=100.0, lm_lambda=1e-4, max_update=1.0, eps=1e-5,
+                  out=None, slot=0):
+    """The grouped LM step (include/rnnpose_hip.h: rnnpose_lm_step_views_io_f32): ONE increment per group of views, solved from the summed
+    systems of the group's views.  groups: an ops.ViewGroups over the B rows.  rgbd: None = the plain sums, or a dict of lm_step_rgbd's
+    depth arguments (obs_depth, theta, K_obs and optionally src_index, index_rows, depth_weight, depth_gate, edge_tol): the depth term
+    composes, it is per view.  num_iters >= 1.
+    -> (G_new (B,4,4), Hm (B,6,6), bv (B,6), Hg (n_groups,6,6), bg (n_groups,6), xi (n_groups,6), info (n_groups,)[, dstats (B,2)]) of
+    the last iteration; out: optional preallocated views of these to write into; slot: workspace slot, as for lm_step."""
+    if not isinstance(groups, ViewGroups):
+        raise TypeError("lm_step_views: groups must be an ops.ViewGroups")
+    if int(num_iters) < 1:
+        raise ValueError("lm_step_views: num_iters must be >= 1")
+    target, weight, depth, K, B, H, W, mode, ws, n = _lm_front(target, weight, depth, K, slot)
+    if len(groups) != B:
+        raise ValueError(f"lm_step_views: the groups cover {len(groups)} views, the batch holds {B}")
+    ng = groups.n_groups
+    if rgbd is not None:
+        r = dict(DEPTH_TERM_DEFAULTS, src_index=None, index_rows=None)
+        extra = set(rgbd) - set(r) - {"obs_depth", "theta", "K_obs"}
+        if extra or not {"obs_depth", "theta", "K_obs"} <= set(rgbd):
+            raise ValueError(f"lm_step_views: rgbd needs obs_depth, theta, K_obs and takes {sorted(r)}; unknown keys {sorted(extra)}")
+        r.update(rgbd)
+        obs_depth, theta, K_obs, idx, S, Ho, Wo = _rgbd_args("lm_step_views", B, r["obs_depth"], r["theta"], r["K_obs"], r["src_index"],
+                                                             r["index_rows"], r["depth_weight"], r["depth_gate"], r["edge_tol"])
+        dargs = (_ptr(obs_depth), _ptr(idx), _ptr(theta), _ptr(K_obs), S, Ho, Wo, float(r["depth_weight"]), float(r["depth_gate"]),
+                 float(r["edge_tol"]))
+    else:
+        dargs = (_ptr(None), _ptr(None), _ptr(None), _ptr(None), 0, 0, 0, 0.0, 0.0, 0.0)
+    Gin = _pose_in(G)
+    dev = depth.device
+    if out is not None:
+        outs = tuple(out)
+    else:
+        outs = _lm_out(None, B, dev, "G Hm bv") + _lm_out(None, ng, dev, "Hm bv xi info") + (_lm_out(None, B, dev, "dstats") if rgbd is not None else ())
+    Gd, Hm, bv, Hg, bg, xi, info = outs[:7]
+    dstats = outs[7] if rgbd is not None else None
+    per_px = 32.0 if rgbd is not None else 16.0
+    _launch("rnnpose_lm_step_views_io_f32", _ptr(target), mode, _ptr(weight), _ptr(depth), eps, _ptr(K), _ptr(Gin), _ptr(Gd), B, H, W,
+            int(num_iters), float(ep_lambda), float(lm_lambda), float(max_update), *dargs, _ptr(groups.group_start), ng, _ptr(groups.E),
+            _ptr(ws), n, _ptr(Hm), _ptr(bv), _ptr(Hg), _ptr(bg), _ptr(xi), _ptr(info), _ptr(dstats), _stream(),
+            nbytes=per_px * B * H * W * int(num_iters), work=(300.0 if rgbd is not None else 200.0) * B * H * W * int(num_iters))
+    return outs[:8] if rgbd is not None else outs[:7]
+
+
 _lm_fused_env_applied = False
 
 

@@ -261,17 +261,22 @@ class PoseRefiner(nn.Module):
         info = small[o[4]:o[5]].view(torch.int32).view(B)
         return flow_up, wmap, Gn, Hm, bv, xi, info
 
-    def _loop_buffers(self, B, H, W, h, w, n, dev, rgbd=None):
+    def _loop_buffers(self, B, H, W, h, w, n, dev, rgbd=None, vg=None):
         """Output / scratch buffers of the n inner iterations of one outer iteration: big (n, B*3*H*W) and small (n, .)
         rows = iteration i (see _out_views); coords (n,B,2,h,w) the re-projected low-res coordinates; with the depth term, dstats
-        (n,B,2) fp64 its statistics."""
+        (n,B,2) fp64 its statistics; with view groups, vsys: the rig-frame systems Hg (n,ng,6,6), bg (n,ng,6) fp64, xi (n,ng,6), info
+        (n,ng) -- the per-view xi / info of `small` are then not written by the step and stay zero."""
         big = torch.empty(n, B * 3 * H * W, device=dev, dtype=torch.float32)
-        small = torch.empty(n, -(-B * 428 // 16) * 16, device=dev, dtype=torch.uint8)     # rows 16-byte aligned (fp64 views)
+        small = (torch.empty if vg is None else torch.zeros)(n, -(-B * 428 // 16) * 16, device=dev, dtype=torch.uint8)     # rows 16-byte aligned (fp64 views)
         extra = {} if rgbd is None else dict(dstats=torch.empty(n, B, 2, device=dev, dtype=torch.float64))
+        if vg is not None:
+            ng = vg["groups"].n_groups
+            extra["vsys"] = dict(Hg=torch.empty(n, ng, 6, 6, device=dev, dtype=torch.float64), bg=torch.empty(n, ng, 6, device=dev, dtype=torch.float64),
+                                 xi=torch.empty(n, ng, 6, device=dev, dtype=torch.float32), info=torch.empty(n, ng, device=dev, dtype=torch.int32))
         return dict(big=big, small=small, coords=torch.empty(n, B, 2, h, w, device=dev, dtype=torch.float32),
                     views=[self._out_views(big[i], small[i], B, H, W) for i in range(n)], **extra)
 
-    def _half_loop(self, bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, single, rgbd=None):
+    def _half_loop(self, bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, single, rgbd=None, vg=None):
         """Generator: the COMPLETE inner loop of images [b0, b1) on stream `st` -- re-projection of their poses -> window
         lookup -> update block -> up-sampling -> descriptor weight -> LM step, n times (PoseRefiner.py:315-362).  Images are
         independent, so nothing synchronises the batch halves per iteration: each half runs its own loop on its own stream
@@ -282,6 +287,9 @@ class PoseRefiner(nn.Module):
         B = depth.shape[0]
         opt = self.cfg.OPTIM_ITER_COUNT
         Gc = G3[b0:b1]
+        if vg is not None:          # the chain's groups (its rows are group-aligned: _chains) and their rows of the rig-frame systems
+            part = vg["groups"].rows(b0, b1)
+            g0, g1_ = vg["groups"].host.index(b0), vg["groups"].host.index(b1)
         for i in range(n):
             flow_up, wmap, Gn, Hm, bv, xi, info = (t[b0:b1] for t in bufs["views"][i])
             if eng.fused_induced and not eng.fused_lookup:      # r06: :324-328 + CFNet.py:136-144 evaluated inside the lookup / flow-feature launches
@@ -293,7 +301,17 @@ class PoseRefiner(nn.Module):
             yield from eng.half_gen(self.cf_net.corr_fn, coords1, B, b0, b1, st, flow_up, single=single, induced=ic)
             ops.corr_weight(g1[b0:b1], g2[b0:b1], flow_up, depth[b0:b1], self.sigma[0], out=wmap)                      # :342-345
             yield
-            if rgbd is None:
+            if vg is not None:        # ONE increment per group of views from their summed systems; the depth term composes
+                shared = rgbd is not None and rgbd["index"] is not None
+                dkw = None if rgbd is None else dict(obs_depth=rgbd["obs"] if shared else rgbd["obs"][b0:b1], theta=rgbd["theta"][b0:b1],
+                                                     K_obs=rgbd["K_obs"][b0:b1], src_index=rgbd["index"],
+                                                     index_rows=(b0, b1) if shared else None, **rgbd["params"])
+                vs = bufs["vsys"]
+                ops.lm_step_views(flow_up, wmap, depth[b0:b1], K[b0:b1], Gc, part, rgbd=dkw, num_iters=opt, ep_lambda=ep_l, lm_lambda=lm_l,
+                                  max_update=1.0, eps=EPS, slot=b0,
+                                  out=(Gn, Hm, bv, vs["Hg"][i, g0:g1_], vs["bg"][i, g0:g1_], vs["xi"][i, g0:g1_], vs["info"][i, g0:g1_]) +
+                                  (() if rgbd is None else (bufs["dstats"][i, b0:b1],)))
+            elif rgbd is None:
                 ops.lm_step(flow_up, wmap, depth[b0:b1], K[b0:b1], Gc, num_iters=opt, ep_lambda=ep_l, lm_lambda=lm_l,
                             max_update=1.0, eps=EPS, out=(Gn, Hm, bv, xi, info), slot=b0)                               # :349-356
             else:        # the same step with the 3-D residual of the observed depth
@@ -305,31 +323,40 @@ class PoseRefiner(nn.Module):
             yield
             Gc = Gn
 
-    def _loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
+    def _chains(self, B, vg):
+        """The image ranges of the concurrent chains; with view groups every cut lies on a group start (a group never straddles two
+        chains).  The eager loop, the capture, the buffers and the workspace slots all take their cuts from here."""
+        return self.cf_net.engine().halves(B, cuts=vg["groups"].host if vg is not None else None)
+
+    def _loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None, vg=None):
         """Eager launches of the n inner iterations -> (big, small); the batch halves' launches are issued alternately."""
         B, dev = depth.shape[0], depth.device
         eng = self.cf_net.engine()
-        bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd)
+        bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd, vg)
         G3 = G.reshape(-1, 4, 4)
-        hv = eng.halves(B)
+        hv = self._chains(B, vg)
         main = torch.cuda.current_stream()
         jobs = []
         for k, (b0, b1) in enumerate(hv):
             st = main if k == 0 else streams.helper_stream(dev, k)
-            jobs.append((self._half_loop(bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd), st))
+            jobs.append((self._half_loop(bufs, b0, b1, st, depth, K, g1, g2, G3, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd, vg), st))
         streams.run_interleaved(jobs, main)
         if rgbd is not None:
             rgbd["stats"] = bufs["dstats"]
+        if vg is not None:
+            vg["system"] = bufs["vsys"]
         return bufs["big"], bufs["small"]
 
-    def _inner_loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
+    def _inner_loop(self, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None, vg=None):
         """-> list of n tuples (flow_up, wmap, G, Hm, bv, xi, info): eager launches, or one replayed hipGraph PER BATCH HALF
         (each a linear chain on its own stream) per outer iteration.  rgbd (the depth term's inputs: obs, theta, K_obs, index,
-        params) receives `stats`, the (n,B,2) statistics; its tensors are inputs of the graph like depth and K."""
+        params) receives `stats`, the (n,B,2) statistics; its tensors are inputs of the graph like depth and K.  vg (groups: the
+        ops.ViewGroups) receives `system`, the rig-frame systems of the n iterations; group_start and E are inputs of the graph like K,
+        the group layout is part of its key."""
         B, H, W = depth.shape[0], depth.shape[-2], depth.shape[-1]
         unpack = lambda big, small: [self._out_views(big[i], small[i], B, H, W) for i in range(n)]
         if not self.use_graph or ops.profiling():
-            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd))
+            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd, vg))
         eng = self.cf_net.engine()
         key = (depth.data_ptr(), K.data_ptr(), g1.data_ptr(), g2.data_ptr(), self.cf_net.corr_fn._buf.data_ptr(),
                tuple(depth.shape), n, self.cfg.OPTIM_ITER_COUNT, float(ep_l), float(lm_l), eng.buffer_key(), self._wkey)
@@ -338,6 +365,10 @@ class PoseRefiner(nn.Module):
             ptrs = tuple(rgbd[k].data_ptr() for k in ("obs", "theta", "K_obs")) + (rgbd["index"].dev.data_ptr() if rgbd["index"] is not None else 0,)
             key += ("rgbd", tuple(rgbd["obs"].shape), rgbd["index"] is not None, tuple(sorted(rgbd["params"].items()))) + ptrs
             tail = len(ptrs)
+        if vg is not None:                      # the group layout, then the addresses of group_start and E
+            vptrs = (vg["groups"].group_start.data_ptr(), vg["groups"].E.data_ptr())
+            key = key[:len(key) - tail] + ("views", vg["groups"].key()) + key[len(key) - tail:] + vptrs
+            tail += len(vptrs)
         skey = key[5:len(key) - tail]           # everything but the addresses: one record per shape
         rec = self._shapes.get(skey)
         if rec is None:
@@ -351,16 +382,16 @@ class PoseRefiner(nn.Module):
                 # the views keep moving (a renderer that allocates fresh tensors every outer iteration): re-capturing per
                 # pointer set would cost more than it saves.  Switch to ONE graph set over persistent input buffers and pay
                 # a device copy of depth / K / descriptors (~0.65 GB at 480x640, B=8: ~0.25 ms) per outer iteration.
-                sb = self._static_inputs(rec, depth, K, g1, g2, rgbd)
+                sb = self._static_inputs(rec, depth, K, g1, g2, rgbd, vg)
                 stkey = ("static",) + key[4:len(key) - tail]
                 gr = rec["static"]
                 if gr is None or gr["key"] != stkey:
-                    gr = rec["static"] = self._capture(stkey, sb["depth"], sb["K"], sb["g1"], sb["g2"], G, h, w, ep_l, lm_l, n, sb.get("rgbd"))
+                    gr = rec["static"] = self._capture(stkey, sb["depth"], sb["K"], sb["g1"], sb["g2"], G, h, w, ep_l, lm_l, n, sb.get("rgbd"), sb.get("vg"))
             else:
                 rec["captures"] += 1
-                gr = rec["gr"] = self._capture(key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd)
+                gr = rec["gr"] = self._capture(key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd, vg)
         if gr is None:                         # capture refused: eager launches from now on (use_graph is off)
-            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd))
+            return unpack(*self._loop(depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd, vg))
         gr["G"].copy_(G.reshape(-1, 4, 4))
 
         def replay(graph):
@@ -372,17 +403,25 @@ class PoseRefiner(nn.Module):
         # copies (the reference returns distinct tensors per iteration): two device copies per OUTER iteration
         if rgbd is not None:
             rgbd["stats"] = gr["bufs"]["dstats"].clone()
+        if vg is not None:
+            vg["system"] = {k: v.clone() for k, v in gr["bufs"]["vsys"].items()}
         return unpack(gr["bufs"]["big"].clone(), gr["bufs"]["small"].clone())
 
-    def _static_inputs(self, rec, depth, K, g1, g2, rgbd=None):
+    def _static_inputs(self, rec, depth, K, g1, g2, rgbd=None, vg=None):
         """Persistent copies (per shape record) of the per-outer-iteration inputs of the inner graph; refreshed when the sources change.
         With the depth term: also of the observed depth, the crop maps, the full-frame intrinsics and the frame index (sb["rgbd"])."""
         more = [] if rgbd is None else [rgbd["obs"], rgbd["theta"], rgbd["K_obs"]] + ([rgbd["index"].dev] if rgbd["index"] is not None else [])
-        shapes = (tuple(depth.shape), tuple(K.shape), tuple(g1.shape), tuple(g2.shape)) + tuple(tuple(t.shape) for t in more)
+        if vg is not None:          # (last: the camera-from-rig transforms; group_start is fixed by the layout, which is part of `shapes`)
+            more = more + [vg["groups"].E]
+        shapes = (tuple(depth.shape), tuple(K.shape), tuple(g1.shape), tuple(g2.shape)) + tuple(tuple(t.shape) for t in more) + \
+            ((vg["groups"].key(),) if vg is not None else ())
         sb = rec["sbuf"]
         if sb is None or sb["shapes"] != shapes:
             sb = rec["sbuf"] = dict(shapes=shapes, depth=torch.empty_like(depth), K=torch.empty_like(K),
                                     g1=torch.empty_like(g1), g2=torch.empty_like(g2), src=None, more=[torch.empty_like(t) for t in more])
+            if vg is not None:
+                gsrc = vg["groups"]
+                sb["vg"] = dict(groups=ops.ViewGroups.from_device(gsrc.group_start.clone(), sb["more"][-1], gsrc.host, gsrc.E_host))
             rec["static"] = None
         src = (depth.data_ptr(), K.data_ptr(), g1.data_ptr(), g2.data_ptr(), depth._version, K._version, g1._version, g2._version) + \
             tuple(t.data_ptr() for t in more) + tuple(t._version for t in more)
@@ -397,9 +436,11 @@ class PoseRefiner(nn.Module):
             sb["rgbd"] = dict(obs=m[0], theta=m[1], K_obs=m[2], index=index, params=rgbd["params"])
         else:
             sb.pop("rgbd", None)
+        if vg is None:
+            sb.pop("vg", None)
         return sb
 
-    def _capture(self, key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None):
+    def _capture(self, key, depth, K, g1, g2, G, h, w, ep_l, lm_l, n, rgbd=None, vg=None):
         """-> graph record, or None when capture is refused (the caller then runs eager launches).  One hipGraph per batch
         half, each a LINEAR chain captured on the stream it will be replayed on: concurrency between the halves comes from
         the two streams, not from branches inside a graph (a two-branch graph of this length replayed almost serially on
@@ -411,10 +452,10 @@ class PoseRefiner(nn.Module):
         try:
             Gs = G.reshape(-1, 4, 4).clone()
             main = torch.cuda.current_stream()
-            streams.warm_up(lambda: self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, rgbd))      # weight packing, allocator, caches
+            streams.warm_up(lambda: self._loop(depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, rgbd, vg))      # weight packing, allocator, caches
             eng.state_restore(snap)
-            bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd)
-            hv = eng.halves(B)
+            bufs = self._loop_buffers(B, depth.shape[-2], depth.shape[-1], h, w, n, dev, rgbd, vg)
+            hv = self._chains(B, vg)
             graphs = []
             torch.cuda.synchronize()
             for k, (b0, b1) in enumerate(hv):
@@ -424,9 +465,9 @@ class PoseRefiner(nn.Module):
                 graph = torch.cuda.CUDAGraph()
                 cap = torch.cuda.Stream()                  # (torch captures on a side stream of its own and replays on the current one)
                 with torch.cuda.graph(graph, stream=cap):
-                    streams.drain(self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd))
+                    streams.drain(self._half_loop(bufs, b0, b1, cap, depth, K, g1, g2, Gs, h, w, ep_l, lm_l, n, len(hv) == 1, rgbd, vg))
                 graphs.append((graph, st))
-            return dict(key=key, graphs=graphs, G=Gs, bufs=bufs)
+            return dict(key=key, graphs=graphs, G=Gs, bufs=bufs, vg=vg)      # (vg: the groups' device arrays live as long as the graphs)
         except Exception as e:                             # noqa: BLE001 -- any capture failure means "run eagerly"
             import warnings
             warnings.warn(f"hipGraph capture of the refinement iterations failed ({e!r}); running eager launches")
@@ -438,7 +479,7 @@ class PoseRefiner(nn.Module):
 
     @torch.no_grad()
     def forward(self, image, Ts, intrinsics, fea_3d=None, Tj_gt=None, obj_cls=None, geofea_3d=None, geofea_2d=None,
-                image_index=None, depth=None):
+                image_index=None, depth=None, view_groups=None):
         """image (B,3,H0,W0); Ts SE3Sequence (B,1,4,4); intrinsics (B,3,3) -> dict (PoseRefiner.py:366-376).
         depth (S,H0,W0) or (S,1,H0,W0): the OBSERVED depth of the frames `image` holds, in the meshes' unit (<= 0 or non-finite =
         missing), indexed by the same image_index.  Used only by a refiner constructed with depth_term; the dict then has
@@ -448,8 +489,27 @@ class PoseRefiner(nn.Module):
         geofea_3d are one tensor (one class for the whole batch), a list of B (P_b, C) tables, or None when the renderer
         holds resident tables (MeshRenderer.set_vertex_attributes).  image_index=None: S == B, object b crops image b.
         Everything downstream of the render hand-off sees (B, ...) views and is per image, so the batch halves, the
-        graph caches and the inner loop are the ones of a single-class batch of the same size."""
+        graph caches and the inner loop are the ones of a single-class batch of the same size.
+        view_groups: an ops.ViewGroups over the B rows, or a pair (group_of_view or group_start, cam_from_rig):
+        rows of one group are VIEWS of one object from calibrated cameras, cam_from_rig (B,4,4) their camera-from-rig transforms E_v.
+        Every LM step then solves ONE increment per group from the summed systems of its views (ops.lm_step_views; the depth term
+        composes) and the views' poses stay tied, T_v = E_v T_rig.  Initial poses: `Ts` of each group's FIRST view is taken as the
+        truth and the other views start at E_v E_first^-1 Ts_first -- THEIR entries of Ts are ignored.  The dict gains `T_rig`
+        (n_groups,4,4) = E_first^-1 Ti_pred[first view] and `view_system`, the last (Hg, bg, xi, info).  None: today's path."""
         self._clear()
+        vg = None
+        if view_groups is not None:
+            if not self.fused:
+                raise NotImplementedError("view_groups needs the fused schedule (fused=True)")
+            nB = Ts.G.shape[0]
+            groups = view_groups if isinstance(view_groups, ops.ViewGroups) else ops.ViewGroups(view_groups[0], view_groups[1], nB, Ts.G.device)
+            if len(groups) != nB:
+                raise ValueError(f"view_groups cover {len(groups)} views, the batch holds {nB}")
+            vg = dict(groups=groups)
+            if groups.n_groups < nB:        # tie the views: T_v = (E_v E_first^-1) Ts_first, with the SE(3) kernels
+                first = groups.first_of_view()
+                rel = ops.se3_compose(groups.E, ops.se3_inverse(groups.E)[first].contiguous())
+                Ts = Ts.__class__(matrix=ops.se3_compose(rel, Ts.G.reshape(-1, 4, 4)[first].contiguous()).reshape(Ts.G.shape), internal=Ts.internal)
         views_kw = {}
         prep = getattr(self.renderer, "prepare_inputs", None)
         if prep is not None:          # host-side checks first: a batch the render hand-off cannot serve launches nothing
@@ -538,7 +598,7 @@ class PoseRefiner(nn.Module):
                         raise ValueError("depth_term: the renderer's views carry no `theta` (the crop maps); RendererAdapter provides it")
                     rgbd["theta"] = views["theta"]
                 loop = self._inner_loop(syn_depth, intrinsics_crop, geofea1_crop, geofea2_crop, Tij.G, h, w, ep_l, lm_l,
-                                        cfg.ITER_COUNT, rgbd)
+                                        cfg.ITER_COUNT, rgbd, vg)
             for i in range(cfg.ITER_COUNT):
                 self.intrinsics_history.append(intrinsics_crop)
                 syn_depths.append(syn_depth)
@@ -572,6 +632,10 @@ class PoseRefiner(nn.Module):
         extra = {"occlusion_visible": views["occlusion_visible"]} if "occlusion_visible" in views else {}
         if rgbd is not None:
             extra["depth_stats"] = rgbd["stats"][-1]
+        if vg is not None:
+            rows = vg["groups"].first_rows_dev()
+            extra["T_rig"] = ops.se3_compose(ops.se3_inverse(vg["groups"].E[rows].contiguous()), Ti.G.reshape(-1, 4, 4)[rows].contiguous())
+            extra["view_system"] = tuple(vg["system"][k][-1] for k in ("Hg", "bg", "xi", "info"))
         return {
             **extra,
             "Tij": Tij,

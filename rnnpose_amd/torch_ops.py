@@ -34,6 +34,7 @@ _SCHEMAS = {
     "bop_vsd": "(Tensor depth_est, Tensor depth_gt, Tensor depth_obs, Tensor src_index, Tensor K, Tensor diameter, float delta, float[] taus) -> (Tensor err, Tensor counts)",
     "lm_step": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
     "lm_step_rgbd": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor obs_depth, Tensor theta, Tensor K_obs, Tensor? src_index=None, float depth_weight=1.0, float depth_gate=0.05, float edge_tol=0.02, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor depth_stats)",
+    "lm_step_views": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor group_start, Tensor cam_from_rig, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor Hg, Tensor bg)",
 }
 
 
@@ -91,6 +92,16 @@ def _lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_inde
     Gn, _, _, xi, _, dstats = ops.lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_index, depth_weight, depth_gate,
                                                edge_tol, num_iters, ep_lambda, lm_lambda, max_update)
     return Gn.reshape(G.shape), xi, dstats
+
+
+def _lm_step_views(target, weight, depth, K, G, group_start, cam_from_rig, num_iters=1, ep_lambda=100.0, lm_lambda=1e-4, max_update=1.0):
+    """group_start: (n_groups + 1,) integer tensor, cam_from_rig (B,4,4): checked on the host (ValueError) before anything is launched.
+    The plain sums; the depth-aware grouped step is ops.lm_step_views(..., rgbd=)."""
+    if group_start.dim() != 1 or int(group_start[-1]) != depth.shape[0]:
+        raise ValueError(f"lm_step_views: group_start must be 1-D and end at the number of views {depth.shape[0]}")
+    groups = ops.ViewGroups(group_start, cam_from_rig, depth.shape[0], depth.device)
+    Gn, _, _, Hg, bg, xi, _ = ops.lm_step_views(target, weight, depth, K, G, groups, None, num_iters, ep_lambda, lm_lambda, max_update)
+    return Gn.reshape(G.shape), xi, Hg, bg
 
 
 def _zoom_crop(x, theta, crop_size, src_index=None):
@@ -160,6 +171,12 @@ def _f_lm_step_rgbd(target, weight, depth, K, G, obs_depth, theta, K_obs, src_in
     return G.new_empty(G.shape, dtype=torch.float32), G.new_empty((B, 6), dtype=torch.float32), G.new_empty((B, 2), dtype=torch.float64)
 
 
+def _f_lm_step_views(target, weight, depth, K, G, group_start, cam_from_rig, num_iters=1, ep_lambda=100.0, lm_lambda=1e-4, max_update=1.0):
+    ng = group_start.shape[0] - 1
+    return (G.new_empty(G.shape, dtype=torch.float32), G.new_empty((ng, 6), dtype=torch.float32), G.new_empty((ng, 6, 6), dtype=torch.float64),
+            G.new_empty((ng, 6), dtype=torch.float64))
+
+
 def _f_zoom_crop(x, theta, crop_size, src_index=None):
     return x.new_empty((theta.shape[0], x.shape[1], int(crop_size[0]), int(crop_size[1])), dtype=torch.float32)
 
@@ -189,7 +206,7 @@ def register():
              "convex_upsample": (_convex_upsample, _f_convex_upsample), "induced_flow": (_induced_flow, _f_induced_flow),
              "corr_weight": (_corr_weight, _f_corr_weight), "lm_normal_eq": (_lm_normal_eq, _f_lm_normal_eq),
              "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step),
-             "lm_step_rgbd": (_lm_step_rgbd, _f_lm_step_rgbd),
+             "lm_step_rgbd": (_lm_step_rgbd, _f_lm_step_rgbd), "lm_step_views": (_lm_step_views, _f_lm_step_views),
              "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
              "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd)}
     for name, schema in _SCHEMAS.items():

@@ -163,6 +163,83 @@ def depth_bench(a, models, cfg, net, hip, items, given, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def views_bench(a, models, cfg, net, size):
+    """--views: one frame, 4 objects x 2 cameras (the rig turned by +-10 degrees about the scene centre): refine_frame grouped by
+    object_id against the same items ungrouped (the parent's behaviour); the LM step alone at B = 8, 480 x 640 on synthetic inputs
+    (every pixel valid): the fused step, its three-launch form and the grouped step in the layouts [2] x 4 and [4] x 2, plain and
+    depth-aware.  (grouped - three-launch form + finalize + solve) bounds the tail kernel; nothing is compared against a threshold."""
+    import dataclasses
+    H, W = size
+    hip = ee.HipEpoch(models, cfg=cfg, desc2d=net)
+    cams = []
+    for deg in (10.0, -10.0):
+        E = ee_rot_y(deg)
+        c = np.array([0.0, 0.0, 0.83])
+        E[:3, 3] = c - E[:3, :3] @ c
+        cams.append(E)
+    items = ee.synthetic_scenes(models, 1, 4, image_size=(H, W), seed=3, renderer=hip.renderer, cameras=cams)
+    dev = {}
+    put = lambda t: dev.setdefault(id(t), t.cuda())
+    grouped = [dataclasses.replace(it, image=put(it.image), geofea_2d=put(it.geofea_2d), depth=None) for it in items]
+    ungrouped = [dataclasses.replace(it, object_id=None, cam_from_rig=None) for it in grouped]
+    hip_off = ee.HipEpoch(models, cfg=cfg, desc2d=net)
+    hip_off.refiner.load_state_dict(hip.refiner.state_dict())
+    whole = time_alternately({"ungrouped": lambda: hip_off.refine_frame(ungrouped), "grouped": lambda: hip.refine_frame(grouped)}, a.runs, a.warmup)
+    # the step alone
+    B, reps = 8, 50
+    depth = torch.ones(B, 1, H, W, device="cuda")
+    flow = torch.zeros(B, 2, H, W, device="cuda")
+    wgt = torch.ones(B, H, W, device="cuda")
+    K = torch.tensor([[572.4, 0, W / 2.0], [0, 573.6, H / 2.0], [0, 0, 1]], device="cuda").repeat(B, 1, 1)
+    G = torch.eye(4, device="cuda").repeat(B, 1, 1)
+    Ecam = torch.as_tensor(np.stack([cams[v % 2] for v in range(B)]).astype(np.float32))
+    theta = torch.tensor([[1.0, 0, 0], [0, 1.0, 0]], device="cuda").repeat(B, 1, 1)
+    rg = dict(obs_depth=torch.ones(B, H, W, device="cuda"), theta=theta, K_obs=K)
+    fns = {}
+    outs = {"lm_step": tuple(torch.empty_like(x) for x in ops.lm_step(flow, wgt, depth, K, G)),
+            "lm_step_rgbd": tuple(torch.empty_like(x) for x in ops.lm_step_rgbd(flow, wgt, depth, K, G, rg["obs_depth"], theta, K))}
+
+    def loop(fn):
+        def run():
+            for _ in range(reps):
+                fn()
+        return run
+    fns["lm_step"] = loop(lambda: ops.lm_step(flow, wgt, depth, K, G, out=outs["lm_step"]))
+    fns["lm_step_rgbd"] = loop(lambda: ops.lm_step_rgbd(flow, wgt, depth, K, G, rg["obs_depth"], theta, K, out=outs["lm_step_rgbd"]))
+    for tag, sizes in (("2x4", [2] * 4), ("4x2", [4] * 2)):
+        gr = ops.ViewGroups([0] + list(np.cumsum(sizes)), Ecam, B, "cuda")
+        for term, kw in (("plain", {}), ("depth", dict(rgbd=rg))):
+            o = tuple(torch.empty_like(x) for x in ops.lm_step_views(flow, wgt, depth, K, G, gr, **kw))
+            fns[f"views_{tag}_{term}"] = loop(lambda gr=gr, kw=kw, o=o: ops.lm_step_views(flow, wgt, depth, K, G, gr, out=o, **kw))
+    alone = time_alternately(fns, a.runs, a.warmup)
+    ops.lm_fused_tail(False)
+    try:
+        unfused = time_alternately({"lm_step_three_launches": fns["lm_step"], "lm_step_rgbd_three_launches": fns["lm_step_rgbd"]}, a.runs, a.warmup)
+    finally:
+        ops.lm_fused_tail(True)
+    alone.update(unfused)
+    med = lambda r, k: r[k]["median_ms"]
+    us = {k: med(alone, k) * 1e3 / reps for k in alone}
+    res = dict(device=torch.cuda.get_device_name(0), objects=4, cameras=2, size=[H, W], crop=list(cfg.zoom_crop_size),
+               schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT], runs=a.runs, warmup=a.warmup, refine_frame=whole,
+               added_ms=med(whole, "grouped") - med(whole, "ungrouped"), step_alone_B8=alone, launches_per_window=reps, us_per_step=us,
+               note="refine_frame ungrouped = the parent's behaviour on the same 8 items, timed alternately with grouped in every run; the "
+                    "step alone: back-to-back eager launches on one stream (launch overhead included in all), B = 8 at the frame size")
+    print(f"refine_frame ungrouped {med(whole, 'ungrouped'):8.2f} ms   grouped {med(whole, 'grouped'):8.2f} ms   added {res['added_ms']:+.3f} ms")
+    for k, v in us.items():
+        print(f"  {k:32s} {v:8.1f} us per step")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+def ee_rot_y(deg):
+    a = np.deg2rad(deg)
+    E = np.eye(4)
+    E[0, 0], E[0, 2], E[2, 0], E[2, 2] = np.cos(a), np.sin(a), -np.sin(a), np.cos(a)
+    return E
+
+
 def bop_bench(a, models, hip, items, size, cover):
     """--bop: the BOP errors of the frame's objects at their initial poses"""
     import time
@@ -227,6 +304,7 @@ def main():
     ap.add_argument("--occlusion", action="store_true", help="measure the occlusion mask between the objects instead (see above)")
     ap.add_argument("--bop", action="store_true", help="time the BOP pose-error functions of the frame instead (see above)")
     ap.add_argument("--depth", action="store_true", help="measure the depth term of the LM step instead (see above)")
+    ap.add_argument("--views", action="store_true", help="measure multi-view refinement instead: 4 objects x 2 cameras, grouped against ungrouped")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -236,6 +314,8 @@ def main():
     models = ee.synthetic_models(NAMES[:min(n, len(NAMES))], sub=a.sub)
     cfg = default_config(RENDER_ITER_COUNT=3, ITER_COUNT=4, OPTIM_ITER_COUNT=1, render_image_size=(H, W), zoom_crop_size=(240, 240))
     net = SuperPoint2D(dict(input_dim=3, descriptor_dim=32, normalize_output=True, use_instance_norm=True), compute_scores=False).cuda().eval()
+    if a.views:
+        return views_bench(a, models, cfg, net, (H, W))
     hip = ee.HipEpoch(models, cfg=cfg, desc2d=net)
     items = ee.synthetic_scenes(models, 1, n, image_size=(H, W), seed=3, renderer=hip.renderer)
     image_dev, g2_dev = items[0].image.cuda(), items[0].geofea_2d.cuda()
