@@ -389,11 +389,29 @@ int rnnpose_conv_pack_weights_f16x3(const float* w_oihw, int c_out, int c_in, in
 int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* h_desc, rnnpose_stream_t stream);
 
 /* fp16x3 range guard.  Activations are split as x*a_scale = hi + lo in fp16: |x*a_scale| > 65504 does not fit, the hi
- * part is clamped and the result is WRONG (the reference computes in fp32 and has no such cliff).  With the check
- * enabled, every launch of the fp16x3 kernels (convolution, encoder stem, correlation-volume operand split) counts the
- * input quads it had to clamp (or that were not finite) in a device counter; rnnpose_f16x3_saturation_count
- * synchronises `stream`, returns the count since the last reset and optionally resets it.  Off by default (the test costs
- * ~3 vector instructions per staged float4).  Process-global switch; not meant to be toggled concurrently with launches. */
+ * part is clamped and the result is WRONG (the reference computes in fp32 and has no such cliff; a NaN even becomes a
+ * finite value).  With the check enabled, every launch that splits fp32 values (convolutions, resident 1x1, lookup +
+ * convc1, mask head, encoder stem, flow features, rnnpose_split_hl_f32, the volume build's operand pre-pass) adds to a
+ * device counter.  WHAT THE NUMBER MEANS:
+ *   - it is ZERO if and only if no element the launch reads inside its windows (channels [c_offset, c_offset + count)
+ *     of the launch's pixels), and no element it writes in split form, has |x * a_scale| > 65504 or is not finite.
+ *     Where src0_mean_rstd is set, the value that is split -- after the fused normalisation + ReLU -- is the one that
+ *     is tested, so what that ReLU turns into 0, a NaN included, is in range.  Channels outside the windows, rows
+ *     behind the launch's last pixel, halo / padding positions, the padding rows of a ragged tile and the positions of
+ *     a flow-feature row segment past the line's end never count.  A launch with src_bounded set counts nothing, and a
+ *     consumer with src_hl checks nothing on its inputs (they arrive split: their producer's epilogue was the check);
+ *   - it is EXACT -- the number of offending quads (4 consecutive channels of a pixel; an 8-channel group for
+ *     rnnpose_split_hl_f32 and the pixel-major pre-pass, an element for the NCHW pre-pass, a window tap for lookup +
+ *     convc1, a channel's 20-pixel row segment for the flow-feature output) -- for the kernels that stage every value
+ *     once: resident 1x1, lookup + convc1, mask head, flow features, rnnpose_split_hl_f32, the pre-pass, and the
+ *     split-form OUTPUTS of every kernel;
+ *   - elsewhere (fp32 sources of the 128-row and strip convolutions, the stem) it is a MULTIPLE of that: a quad is
+ *     counted once per staging, i.e. per tap of a 1x5 / 5x1 / stride-2 layer, per 3x3 halo tile or strip patch that
+ *     holds it, per share of a K split, per overlapping stem patch (only the first column tile of a row tile counts,
+ *     so not per column tile).
+ * rnnpose_f16x3_saturation_count synchronises `stream`, returns the count since the last reset and optionally resets
+ * it.  The library starts with the check off; the Python package switches it on (the test costs ~3 vector
+ * instructions per staged float4).  Process-global switch; not meant to be toggled concurrently with launches. */
 int rnnpose_f16x3_saturation_check(int enable);
 int rnnpose_f16x3_saturation_count(unsigned long long* h_count, int reset, rnnpose_stream_t stream);
 /* Device-side read of the same counter: copies it into *d_count (DEVICE memory) on `stream`, no host synchronisation --

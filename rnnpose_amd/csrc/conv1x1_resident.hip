@@ -48,6 +48,7 @@ __global__ __launch_bounds__(8 * MQ) __attribute__((amdgpu_num_vgpr(160))) void 
   }
   __builtin_amdgcn_sched_barrier(0);
   int sat_n = 0;
+  const bool row_in = m0 + (tid >> 3) < p.out.M;                     // range guard: a padding row (a re-read of the last pixel) is not counted again
   {
     const int r = tid >> 3;
     const int chunk = (c4 >> 1) ^ (((r >> 2) & 1) << 1);            // rows r and r + 4 would share LDS banks: swap chunk pairs
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(8 * MQ) __attribute__((amdgpu_num_vgpr(160))) void 
       const float4 v = in ? av[cb] : make_float4(0.f, 0.f, 0.f, 0.f);
       h4 hi, lo;
       split4(v, p.out.a_scale, hi, lo);
-      if (p.out.sat && in) sat_n += rp::quad_saturates(v, p.out.a_scale) ? 1 : 0;
+      if (p.out.sat && in && row_in) sat_n += rp::quad_saturates(v, p.out.a_scale) ? 1 : 0;
       *reinterpret_cast<h4*>(&sA[cb][0][off]) = hi;
       *reinterpret_cast<h4*>(&sA[cb][1][off]) = lo;
     }

@@ -87,7 +87,7 @@ using namespace rpconv;
 // block instead of three (the row-major tiling staged a separate tile per kernel row), a third of the activation traffic, and
 // no tap masks at all.  r03 ablation: the staging is 20-25 % of a 3x3 layer (17 % of a 1x5 one, which already stages once).
 constexpr int SPR = 180, SPW = 18;      // halo tile rows, halo tile width
-template <int NI, bool STRIDED, bool COLS4 = false, int TT = 0, bool NORM = false, bool HLIN = false, bool DEEP = false,
+template <int NI, bool STRIDED, bool COLS4 = false, int TTS = 0, bool NORM = false, bool HLIN = false, bool DEEP = false,
           bool SPATIAL = false>
 #ifndef RP_COLS4_WAVES
 #define RP_COLS4_WAVES 2      // waves per SIMD the 4-column layout is compiled for (3: 168 VGPRs with 60-90 spilled once the statistics are fp64; 2: none; measured equal)
@@ -96,7 +96,13 @@ template <int NI, bool STRIDED, bool COLS4 = false, int TT = 0, bool NORM = fals
 #define RP_SP_SINGLE 0        // 1: patch-tiled 3x3 layers (2x2 waves) keep ONE halo tile in LDS (29 KB, three workgroups per CU, two barriers
 #endif                        // per channel block) instead of a double-buffered one (58 KB, two per CU).  r03 same-box: 669.8 vs 672.4
                               // iters/s, single image 5.20 vs 5.08 ms -- the kernel does not respond to occupancy either; off
-__global__ __launch_bounds__(NT, ((NI == 2 || DEEP || (SPATIAL && (COLS4 || !RP_SP_SINGLE))) ? 2 : (SPATIAL ? 3 : (COLS4 ? (TT == 3 ? 3 : RP_COLS4_WAVES) : (TT > 0 ? 3 : 2))))) void conv_igemm_f16x3_kernel(const KParams p) {
+__global__ __launch_bounds__(NT, ((NI == 2 || DEEP || (SPATIAL && (COLS4 || !RP_SP_SINGLE))) ? 2 : (SPATIAL ? 3 : (COLS4 ? (TTS == 3 ? 3 : RP_COLS4_WAVES) : (TTS != 0 ? 3 : 2))))) void conv_igemm_f16x3_kernel(const KParams p) {
+  // TTS = taps per staged tile (0: run-time loop).  NEGATIVE: the same kernel with the range guard on the NORMALISED quad (NORM only) -- the
+  // instantiations a launch with src0_mean_rstd takes while the guard counts.  With the guard off or src_bounded (the encoder) nothing is
+  // counted and the launch keeps the positive form, the machine code profiles/traffic.json was measured on (tools/isa_equal.py).
+  constexpr int TT = TTS < 0 ? -TTS : TTS;
+  constexpr bool NORM_GUARD = TTS < 0;
+  static_assert(!NORM_GUARD || NORM, "a negative tap count is the guarded form of the fused input normalisation");
   static_assert(!DEEP || (HLIN && !COLS4 && TT >= 3), "the deep pipeline is for split sources, the 2x2 wave layout, 3 or 5 taps");
   static_assert(!SPATIAL || (TT == 9 && !STRIDED && !DEEP), "patch tiling is the 3x3 stride-1 form: nine taps on one staged tile");
   constexpr int ARW = SPATIAL ? SPR : AROWS;            // staged rows
@@ -239,6 +245,9 @@ __global__ __launch_bounds__(NT, ((NI == 2 || DEEP || (SPATIAL && (COLS4 || !RP_
     RP_LOAD_A_ROW(0, S_) RP_LOAD_A_ROW(1, S_) RP_LOAD_A_ROW(2, S_) RP_LOAD_A_ROW(3, S_) RP_LOAD_A_ROW(4, S_) \
     if (SPATIAL) RP_LOAD_A_ROW(5, S_)                                                                       \
   } while (0)
+  // NORM: relu((x - mean) * rstd) of a staged quad -- the value that is split, and so the one the range guard looks at
+#define RP_NORM4(X_) make_float4(fmaxf(((X_).x - nrm01.x) * nrm01.y, 0.f), fmaxf(((X_).y - nrm01.z) * nrm01.w, 0.f), \
+                                 fmaxf(((X_).z - nrm23.x) * nrm23.y, 0.f), fmaxf(((X_).w - nrm23.z) * nrm23.w, 0.f))
 #define RP_STORE_A_ROW(R_, AB_, S_)                                                                         \
   {                                                                                                         \
     const int j_ = (tid >> 3) + 32 * R_;                                                                    \
@@ -253,14 +262,13 @@ __global__ __launch_bounds__(NT, ((NI == 2 || DEEP || (SPATIAL && (COLS4 || !RP_
       h4 hi_, lo_;                                                                                          \
       const float4 z4_ = make_float4(0.f, 0.f, 0.f, 0.f);                                                   \
       float4 xv_ = av##S_##_##R_;                                                                           \
-      if (NORM) xv_ = make_float4(fmaxf((xv_.x - nrm01.x) * nrm01.y, 0.f), fmaxf((xv_.y - nrm01.z) * nrm01.w, 0.f), \
-                                  fmaxf((xv_.z - nrm23.x) * nrm23.y, 0.f), fmaxf((xv_.w - nrm23.z) * nrm23.w, 0.f)); \
+      if (NORM) xv_ = RP_NORM4(xv_);                                                                        \
       split4((amask##S_ >> R_) & 1u ? xv_ : z4_, p.a_scale, hi_, lo_);   /* padding / out-of-range rows: zeros (AFTER the norm) */ \
       *reinterpret_cast<h4*>(sAf + RP_BUF(AB_) * (2 * PRW * RS) + j_ * RS + c4 * 4) = hi_;                        \
       *reinterpret_cast<h4*>(sAf + RP_BUF(AB_) * (2 * PRW * RS) + PRW * RS + j_ * RS + c4 * 4) = lo_;             \
     }                                                                                                       \
   }
-#define RP_SAT_ROW(R_, S_) sat_n += (((amask##S_ >> R_) & 1u) && rp::quad_saturates(av##S_##_##R_, p.a_scale)) ? 1 : 0;
+#define RP_SAT_ROW(R_, S_) sat_n += (((amask##S_ >> R_) & 1u) && rp::quad_saturates(NORM_GUARD ? RP_NORM4(av##S_##_##R_) : av##S_##_##R_, p.a_scale)) ? 1 : 0;
 #define RP_STORE_A(AB_, S_)                                                                                 \
   do {                                                                                                      \
     if (!HLIN && sat_here) { RP_SAT_ROW(0, S_) RP_SAT_ROW(1, S_) RP_SAT_ROW(2, S_) RP_SAT_ROW(3, S_) RP_SAT_ROW(4, S_) if (SPATIAL) RP_SAT_ROW(5, S_) }   /* uniform branch, VALU only */ \
@@ -1186,7 +1194,8 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
       if (hlin) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, true, 9, false, true, false, true>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, true, 9, false, false, false, true>), grid, block, 0, st, p);
     } else {
-      if (d->src0_mean_rstd) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, true, false, false, true>), grid, block, 0, st, p);
+      if (d->src0_mean_rstd && p.sat) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, -9, true, false, false, true>), grid, block, 0, st, p);
+      else if (d->src0_mean_rstd) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, true, false, false, true>), grid, block, 0, st, p);
       else if (hlin) hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, false, true, false, true>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 9, false, false, false, true>), grid, block, 0, st, p);
     }
@@ -1206,6 +1215,8 @@ int rnnpose_conv2d_nhwc_f16x3(const rnnpose_conv_desc_t* d, rnnpose_stream_t str
   } else {
     if (p.stride == 2) {
       hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, true, false>), grid, block, 0, st, p);
+    } else if (d->src0_mean_rstd && p.sat) {
+      hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, -3, true>), grid, block, 0, st, p);
     } else if (d->src0_mean_rstd) {
       hipLaunchKernelGGL((conv_igemm_f16x3_kernel<1, false, false, 3, true>), grid, block, 0, st, p);
     } else if (hlin) {

@@ -92,6 +92,7 @@ __global__ __launch_bounds__(8 * MQ, 3) void corr_convc1_kernel(const CParams p)
   const int j0 = g == 0 ? 0 : g + 1, nj = g == 0 ? 2 : 1;
   const int swz = ((r >> 2) & 1) << 1;
   int sat_n = 0;
+  const bool tap_in = m0 + r < p.out.M;                       // range guard: a padding row (the taps of the last pixel again) is not counted again
 
   // ---- MFMA side (resident_tile.cuh): 4 column tiles x 2 pixel tiles x 3 split products = 24 MFMAs per channel block
   const int l15 = lane & 15, lq = lane >> 4;
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(8 * MQ, 3) void corr_convc1_kernel(const CParams p)
       const int off = ((c >> 5) % NSLOT) * SLOT_HALFS + r * 32 + (((k >> 3) ^ swz) << 3) + (k & 7);
       _Float16 hi, lo;
       split1(v, p.out.a_scale, hi, lo);
-      if (p.out.sat) sat_n += !(fabsf(v) <= 65504.f / p.out.a_scale) ? 1 : 0;
+      if (p.out.sat && tap_in) sat_n += !(fabsf(v) <= 65504.f / p.out.a_scale) ? 1 : 0;
       ring[off] = hi;
       ring[off + MQ * 32] = lo;
     });

@@ -93,6 +93,7 @@ __global__ __launch_bounds__(8 * MQ, 3) void mask_upsample_kernel(const MUParams
   }
   __builtin_amdgcn_sched_barrier(0);
   int sat_n = 0;
+  const bool row_in = m0 + (tid >> 3) < total;                       // range guard: a padding row (a re-read of the last pixel) is not counted again
   {
     const int r = tid >> 3;
     const int chunk = (c4 >> 1) ^ (((r >> 2) & 1) << 1);            // rows r and r + 4 would share LDS banks: swap chunk pairs
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(8 * MQ, 3) void mask_upsample_kernel(const MUParams
     for (int cb = 0; cb < NCB; ++cb) {
       h4 hi, lo;
       split4(av[cb], p.a_scale, hi, lo);
-      if (p.sat) sat_n += rp::quad_saturates(av[cb], p.a_scale) ? 1 : 0;
+      if (p.sat && row_in) sat_n += rp::quad_saturates(av[cb], p.a_scale) ? 1 : 0;
       *reinterpret_cast<h4*>(&sA[cb][0][off]) = hi;
       *reinterpret_cast<h4*>(&sA[cb][1][off]) = lo;
     }
@@ -316,13 +317,14 @@ __global__ __launch_bounds__(4 * MQ, 2) void mask_upsample32_kernel(const MUPara
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     const int r = (tid >> 3) + 16 * ps;
+    const bool row_in = m0 + r < total;                                // range guard: padding rows are not counted again
     const int chunk = (c4 >> 1) ^ ((r >> 2) & 3);
     const int off = r * 32 + chunk * 8 + (c4 & 1) * 4;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
       h4 hi, lo;
       split4(av[ps][cb], p.a_scale, hi, lo);
-      if (p.sat) sat_n += rp::quad_saturates(av[ps][cb], p.a_scale) ? 1 : 0;
+      if (p.sat && row_in) sat_n += rp::quad_saturates(av[ps][cb], p.a_scale) ? 1 : 0;
       *reinterpret_cast<h4*>(&sA[cb][0][off]) = hi;
       *reinterpret_cast<h4*>(&sA[cb][1][off]) = lo;
     }

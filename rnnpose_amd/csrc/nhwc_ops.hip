@@ -509,7 +509,7 @@ __global__ __launch_bounds__(128, 3) void conv7x7_cin2_kernel(const float* __res
       rp::h4 hi, lo;
       const float4 q = make_float4(y, 0.f, 0.f, 0.f);
       rp::split4(q, a_scale, hi, lo);
-      sflag |= rp::quad_saturates(q, a_scale);
+      sflag |= X0 + x < w && rp::quad_saturates(q, a_scale);      // (range guard: a position past the line's end is never stored)
       const unsigned mine = odd ? __builtin_bit_cast(unsigned short, lo.x) : __builtin_bit_cast(unsigned short, hi.x);
       const unsigned send = odd ? __builtin_bit_cast(unsigned short, hi.x) : __builtin_bit_cast(unsigned short, lo.x);
       const unsigned got = __shfl_xor(send, 1);          // even lane receives the odd lane's hi, odd lane the even lane's lo

@@ -88,7 +88,11 @@ SOURCES = ["pointwise.hip", "corr_pyramid.hip", "corr_lookup.hip", "corr_convc1.
 EXTRA = ["runtime_host.cpp"]
 # headers that need no host patch but may be named by HOSTEXEC_MUTATE -> the SOURCES that include them: the mutated header is written
 # next to scratch copies of those sources (quote includes look there first)
-MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"], "resident_tile.cuh": ["conv1x1_resident.hip", "corr_convc1.hip"]}
+MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"], "resident_tile.cuh": ["conv1x1_resident.hip", "corr_convc1.hip"],
+                   "conv_common.cuh": ["conv_igemm.hip"],          # (+ the strip sources, which are scratch copies next to their patched header anyway)
+                   "f16x3.cuh": ["nhwc_ops.hip", "stem.hip", "mask_upsample.hip", "corr_pyramid.hip", "conv_igemm.hip", "conv1x1_resident.hip", "corr_convc1.hip"]}
+# a mutated header that other headers include: those are copied next to it, so that THEIR quote include finds the mutated copy too
+HEADER_COMPANIONS = {"f16x3.cuh": ["conv_common.cuh", "resident_tile.cuh"]}
 
 
 def clang() -> str:
@@ -149,11 +153,11 @@ def build(outdir: str) -> str:
         tu = os.path.join(outdir, name + ".host.cpp")
         open(tu, "w").write(f'#include "harness.hpp"\n#include "{src}"\n')
         units.append(tu)
-    if includers:
-        name = mutate.split("::")[0]
+    scratch_headers = ([mutate.split("::")[0]] + HEADER_COMPANIONS.get(mutate.split("::")[0], [])) if includers else []
+    for name in scratch_headers:
         open(os.path.join(outdir, name), "w").write(mutated(name, open(os.path.join(CSRC, name)).read()))
     for name in MUTABLE_HEADERS:                                    # (a stale mutated copy would shadow the header of an unmutated build)
-        if not includers or name != mutate.split("::")[0]:
+        if name not in scratch_headers:
             if os.path.exists(os.path.join(outdir, name)):
                 os.remove(os.path.join(outdir, name))
     for name, patches in HEADER_PATCHES.items():
