@@ -55,7 +55,7 @@ class MeshRenderer:
                  depth_perspective_correct: bool = True, shading: str = "flat"):
         """meshes: {class name: dict(verts (P,3) float, faces (F,3) int, colors (P,3) float in [0,1] or None,
         optional verts_uvs (U,2) float, faces_uvs (F,3) int (uv rows of each face) and texture (Ht,Wt,3) float in [0,1], row 0 =
-        the image's top row as read from the file)}.
+        the image's top row as read from the file)}.  A class without colours renders white, also next to classes that have them.
         shading: "flat" (the two-sided flat-normal terms) or "phong" (PyTorch3D's phong_shading: interpolated vertex normals,
         one-sided); shade=False renders the albedo unshaded.  Textured meshes and shading="phong" render their colour through
         the textured resolve, where a mesh without a texture has its own vertex colours as albedo, or white without them.
@@ -74,7 +74,9 @@ class MeshRenderer:
         self.names = list(meshes)
         vo, fo, verts, faces, cols = {}, {}, [], [], []
         nv = nf = 0
-        self.has_colors = all(meshes[n].get("colors") is not None for n in self.names)
+        # one colour table for the plain entry as soon as ANY class has colours, white rows for the classes without (as the textured
+        # entry's albedo table, _texture_data): with classes of both kinds the coloured ones came out white
+        self.has_colors = any(meshes[n].get("colors") is not None for n in self.names)
         for n in self.names:
             m = meshes[n]
             v = torch.as_tensor(np.asarray(m["verts"], dtype=np.float32))
@@ -87,7 +89,10 @@ class MeshRenderer:
             verts.append(v)
             faces.append(f)
             if self.has_colors:
-                cols.append(torch.as_tensor(np.asarray(m["colors"], dtype=np.float32)).reshape(-1, 3))
+                c = m.get("colors")
+                cols.append(torch.ones(v.shape[0], 3) if c is None else torch.as_tensor(np.asarray(c, dtype=np.float32)).reshape(-1, 3))
+                if cols[-1].shape[0] != v.shape[0]:
+                    raise ValueError(f"mesh {n!r}: colors must be (P,3) with the P of verts")
             nv += v.shape[0]
             nf += f.shape[0]
         self._vo, self._fo = vo, fo

@@ -65,7 +65,8 @@ def _pairs(x0, x1, y0, y1, budget=1 << 21):
 
 def raycast(verts, faces, T, K, H, W, near=0.1, pixel_center=0.5, perspective=True):
     """-> dict: face (H,W) int64 (-1 = miss), z (H,W) (-1 = miss), w (H,W,3), vz (H,W) (0 = miss), certain (H,W) bool, vd_certain (H,W) bool,
-    miss_ok (H,W) bool (no face surely covers the pixel), candidates = dict(pix, face, z, w) over the candidate pairs of every pixel"""
+    miss_ok (H,W) bool (no face surely covers the pixel), candidates = dict(pix, face, z, w) over the candidate pairs of every pixel,
+    cam_z (P,), and per face delta (F,) and alt (F,): delta_f and the smallest projected altitude a_f of the docstring above, in px"""
     faces = np.asarray(faces, np.int64)
     Xc, fx, fy, cx, cy = _camera(verts, T, K)
     if not (np.isfinite(Xc).all()):
@@ -154,14 +155,15 @@ def raycast(verts, faces, T, K, H, W, near=0.1, pixel_center=0.5, perspective=Tr
     ws = np.sort(best_w, 1)
     bf = np.clip(best_f, 0, None)
     with np.errstate(all="ignore"):
-        edge = np.sqrt((tx[bf] - np.roll(tx[bf], 1, 1)) ** 2 + (ty[bf] - np.roll(ty[bf], 1, 1)) ** 2).max(1)
-        alt = np.abs(area[bf]) / edge
+        edge = np.sqrt((tx - np.roll(tx, 1, 1)) ** 2 + (ty - np.roll(ty, 1, 1)) ** 2).max(1)
+        alt_f = np.abs(area) / edge                                             # (F,) smallest projected altitude of every face, px
+        alt = alt_f[bf]
         gap = 2.0 * delta[bf] / alt + 64.0 * EPS
     vd_certain = certain & (~hit | (ws[:, 2] - ws[:, 1] >= gap))
     r = lambda a: a.reshape((H, W) + a.shape[1:])
     return dict(face=r(best_f), z=r(best_z), w=r(best_w), vz=r(vz), hit=r(hit), certain=r(certain), vd_certain=r(vd_certain),
                 miss_ok=r(~np.isfinite(zs)), candidates=dict(pix=pix[cand], face=fid[cand], z=z[cand], w=w[cand]),
-                cam_z=Z, delta=delta)
+                cam_z=Z, delta=delta, alt=alt_f)
 
 
 def interpolate(face, w, faces, attr):
