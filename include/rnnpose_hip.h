@@ -766,6 +766,49 @@ int rnnpose_raster_occlusion_f32(const float* verts, const int* faces, const int
                                  float margin, const void* own_keys, void* workspace, size_t workspace_bytes, float* visible,
                                  int* occluder, float* depth_inout, rnnpose_stream_t stream);
 
+/* ---- Initial poses from 2D-3D descriptor matches: matcher + P3P RANSAC (no counterpart in the reference) ----
+ * rnnpose_desc_match_f32: desc3d (total_points, D) fp32, D = 32, the objects' point descriptors back to back (16-byte aligned),
+ *   points (total_points, 3); object b owns the rows [pt_off[b], pt_off[b+1]) (device int32, B+1 entries, the layout of the
+ *   rasteriser's vert_off; max_points >= the largest count -- an object whose range does not fit gets count = 0);
+ *   desc2d (S, D, H, W) fp32 NCHW; src_index (B) device int32; bbox (B,4) device int32 [xmin, ymin, xmax, ymax], inclusive
+ *   (rnnpose_mask_bbox_f32), clamped to the image IN the kernel; the pixels of the clamped box with (u - xmin) % step == 0 and
+ *   (v - ymin) % step == 0 (xmin, ymin of the CLAMPED box) take part.  An empty box (the mask_bbox sentinel included) or an index
+ *   outside [0, S) gives count = 0 -- THE CALLER checks the index range on the host (rnnpose_amd.ops.desc_match does).
+ *   s(i, j) = sum_k d3[i][k] d2[j][k]: one fp32 fma chain over k = 0..31 from +0.  Forward: every point's best pixel; backward:
+ *   every pixel's best point; equal similarities go to the lowest linear pixel index v W + u / the lowest point index; a NaN
+ *   similarity is never a best.  Point i is a correspondence when s_fwd(i) >= min_sim and, with mutual = 1, the best point of its best
+ *   pixel is i.  Outputs, compacted per object in ascending point index: X (B,M,3) the point, x (B,M,2) = (u + pixel_center,
+ *   v + pixel_center), sim (B,M), point_idx (B,M) the index within the object, count (B) = min(correspondences, M); rows >= count are
+ *   NOT written.  workspace: one 64-bit key per point and per box pixel (rnnpose_desc_match_workspace_bytes, 8-byte aligned).
+ *   Four launches (clear, forward, backward, select).  The maxima across workgroups meet in 64-bit INTEGER atomicMax on
+ *   (orderable similarity bits << 32 | ~index): no floating-point atomics, bit-identical from run to run and independent of B.
+ * rnnpose_pnp_ransac_f64: X (B,M,3), x (B,M,2), count (B) as above (count is clamped to [0, M]); K (B,3,3) (fx, fy, cx, cy; no skew);
+ *   rnd (B,Hyp,3) device uint32: hypothesis h of object b samples the correspondences rnd[b][h][c] % count[b] -- the kernel has no
+ *   generator.  All arithmetic fp64 on values converted from fp32, without fma contraction.  Per hypothesis: repeated indices give no
+ *   candidate; else P3P (Grunert's quartic by polynomial arithmetic, Ferrari's roots polished by Newton, the three distances polished by
+ *   Newton on the distance equations, pose = rigid alignment of the triangles) -> up to four candidates (finite, the three sample depths
+ *   > 0), in the root order csrc/pnp_math.cuh defines; every candidate is scored over all count[b] correspondences: r^2 = |proj(R X + t)
+ *   - x|^2, a point with Z <= 1e-6 is an outlier, MSAC cost = sum min(r^2, tau^2), inliers = #{r^2 < tau^2}; the hypothesis keeps its
+ *   cheapest candidate (the lower root order on a tie).  cost (B,Hyp) fp64 (+inf without a candidate), inliers (B,Hyp) int32.
+ *   Per object: the cheapest hypothesis (the lowest h on a tie) -> best (B) (-1: none); n_polish Gauss-Newton steps on the inliers
+ *   re-selected with tau before every step: left increment exp(xi), xi = (translation, rotation), J = J_proj [I | -[X1]x], own 6x6
+ *   Cholesky.  T (B,4,4) fp32; inlier_mask (B,M) uint8 (rows < count written), n_inliers (B), final_cost (B) fp64: the inlier set and
+ *   the MSAC cost of the FINAL pose; info (B) = 0, or -1 with T[b] NOT written (mask 0, n_inliers 0, final_cost +inf) when
+ *   count[b] < min_count, no hypothesis produced a candidate, or a polish system is not positive definite / the pose not finite.
+ *   workspace: the candidates of every hypothesis (rnnpose_pnp_ransac_workspace_bytes).  Three launches; fixed-order sums.
+ * Both: a null pointer, a bad size, D != 32, step < 1, mutual not 0/1, tau <= 0, min_count < 4, n_polish outside [0,64] or a short
+ *   workspace return 1 and launch nothing; no allocation, no synchronisation. */
+size_t rnnpose_desc_match_workspace_bytes(int total_points, int B, int H, int W, int step);
+int rnnpose_desc_match_f32(const float* desc3d, const float* points, const int* pt_off, int total_points, int max_points,
+                           const float* desc2d, int S, int D, int H, int W, const int* src_index, const int* bbox, int B, int step,
+                           float min_sim, int mutual, float pixel_center, int M, void* workspace, size_t workspace_bytes, float* X,
+                           float* x, float* sim, int* point_idx, int* count, rnnpose_stream_t stream);
+size_t rnnpose_pnp_ransac_workspace_bytes(int B, int Hyp);
+int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
+                           double tau, int n_polish, int min_count, void* workspace, size_t workspace_bytes, float* T, double* cost,
+                           int* inliers, int* best, unsigned char* inlier_mask, int* n_inliers, double* final_cost, int* info,
+                           rnnpose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

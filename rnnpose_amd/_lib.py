@@ -153,6 +153,10 @@ PROTOTYPES = {
     "rnnpose_bop_sym_dist_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _p, _z, _p, _p]),
     "rnnpose_bop_vsd_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "rnnpose_bop_vsd_f64": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _d, _p, _i, _p, _z, _p, _p, _p]),
+    "rnnpose_desc_match_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "rnnpose_desc_match_f32": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _f, _i, _f, _i, _p, _z, _p, _p, _p, _p, _p, _p]),
+    "rnnpose_pnp_ransac_workspace_bytes": (_z, [_i, _i]),
+    "rnnpose_pnp_ransac_f64": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _d, _i, _i, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -16,6 +16,11 @@
 
 #pragma clang fp contract(off)
 
+// the pose initialiser: descriptor matcher and P3P RANSAC.  Their kernels live in headers of their own; the entry
+// points are at the end of this file, so that the host-executed test tier (which builds a fixed list of sources) carries them too.
+#include "desc_match.cuh"
+#include "pnp.cuh"
+
 namespace {
 
 constexpr int NN_TILE = 1024;
@@ -433,6 +438,67 @@ void findNearestPointIdxLauncher(float* ref_pts, float* que_pts, int* idxs, int 
   if (dr) (void)hipFree(dr);
   if (dq) (void)hipFree(dq);
   if (di) (void)hipFree(di);
+}
+
+// ---- pose initialiser: descriptor matcher + P3P RANSAC (csrc/desc_match.cuh, csrc/pnp.cuh) ---------------------------------------
+size_t rnnpose_desc_match_workspace_bytes(int total_points, int B, int H, int W, int step) {
+  return dm::workspace_bytes(total_points, B, H, W, step);
+}
+
+int rnnpose_desc_match_f32(const float* desc3d, const float* points, const int* pt_off, int total_points, int max_points,
+                           const float* desc2d, int S, int D, int H, int W, const int* src_index, const int* bbox, int B, int step,
+                           float min_sim, int mutual, float pixel_center, int M, void* workspace, size_t workspace_bytes, float* X,
+                           float* x, float* sim, int* point_idx, int* count, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_desc_match_f32";
+  RP_REQUIRE(desc3d && points && pt_off && desc2d && src_index && bbox && workspace && X && x && sim && point_idx && count, fn, "null pointer");
+  RP_REQUIRE(D == dm::kD, fn, "D must be 32");
+  RP_REQUIRE(B > 0 && B < 65536 && S > 0 && H > 0 && W > 0 && total_points > 0 && max_points > 0 && max_points <= total_points && M > 0, fn,
+             "bad size");
+  RP_REQUIRE(static_cast<long long>(H) * W < (1ll << 31) && static_cast<long long>(B) * M < (1ll << 31), fn, "bad size (too large)");
+  RP_REQUIRE(step >= 1, fn, "step must be >= 1");
+  RP_REQUIRE(mutual == 0 || mutual == 1, fn, "mutual must be 0 or 1");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(desc3d) % 16 == 0 && reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn,
+             "desc3d must be 16-byte aligned, workspace 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= dm::workspace_bytes(total_points, B, H, W, step), fn, "workspace too small");
+  const int cap = dm::pixel_capacity(H, W, step);
+  RP_REQUIRE(rp::cdiv(cap, dm::kFwdChunk) < 65536 && rp::cdiv(max_points, dm::kBwdChunk) < 65536, fn, "bad size (too large)");
+  hipStream_t st = rp::as_stream(stream);
+  unsigned long long* fwd = static_cast<unsigned long long*>(workspace);
+  unsigned long long* bwd = fwd + total_points;
+  const size_t nkeys = static_cast<size_t>(total_points) + static_cast<size_t>(B) * cap;
+  hipLaunchKernelGGL(dm::dm_clear_kernel, dim3(rp::cdiv(nkeys, 256)), dim3(256), 0, st, fwd, nkeys);
+  hipLaunchKernelGGL(dm::dm_forward_kernel, dim3(rp::cdiv(max_points, 256), rp::cdiv(cap, dm::kFwdChunk), B), dim3(256), 0, st, desc3d, pt_off,
+                     total_points, max_points, desc2d, S, H, W, src_index, bbox, step, fwd);
+  hipLaunchKernelGGL(dm::dm_backward_kernel, dim3(rp::cdiv(cap, 256), rp::cdiv(max_points, dm::kBwdChunk), B), dim3(256), 0, st, desc3d, pt_off,
+                     total_points, max_points, desc2d, S, H, W, src_index, bbox, step, cap, bwd);
+  hipLaunchKernelGGL(dm::dm_select_kernel, dim3(B), dim3(256), 0, st, points, pt_off, total_points, max_points, S, H, W, src_index, bbox, step,
+                     cap, min_sim, mutual, pixel_center, M, fwd, bwd, X, x, sim, point_idx, count);
+  return rp::check_launch(fn);
+}
+
+size_t rnnpose_pnp_ransac_workspace_bytes(int B, int Hyp) { return pnp::workspace_bytes(B, Hyp); }
+
+int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
+                           double tau, int n_polish, int min_count, void* workspace, size_t workspace_bytes, float* T, double* cost,
+                           int* inliers, int* best, unsigned char* inlier_mask, int* n_inliers, double* final_cost, int* info,
+                           rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_pnp_ransac_f64";
+  RP_REQUIRE(X && x && count && K && rnd && workspace && T && cost && inliers && best && inlier_mask && n_inliers && final_cost && info, fn,
+             "null pointer");
+  RP_REQUIRE(B > 0 && B < 65536 && M > 0 && Hyp > 0 && Hyp <= (1 << 22), fn, "bad size");
+  RP_REQUIRE(static_cast<long long>(B) * M < (1ll << 31), fn, "bad size (too large)");
+  RP_REQUIRE(tau > 0.0 && tau - tau == 0.0, fn, "tau must be positive and finite");
+  RP_REQUIRE(n_polish >= 0 && n_polish <= 64, fn, "n_polish must lie in [0, 64]");
+  RP_REQUIRE(min_count >= 4, fn, "min_count must be >= 4");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= pnp::workspace_bytes(B, Hyp), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  pnp::HypRec* rec = static_cast<pnp::HypRec*>(workspace);
+  hipLaunchKernelGGL(pnp::pnp_solve_kernel, dim3(rp::cdiv(Hyp, 64), B), dim3(64), 0, st, X, x, count, M, K, rnd, B, Hyp, min_count, rec);
+  hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
+  hipLaunchKernelGGL(pnp::pnp_polish_kernel, dim3(B), dim3(64), 0, st, X, x, count, M, K, B, Hyp, tau, n_polish, rec, cost, T, best, inlier_mask,
+                     n_inliers, final_cost, info);
+  return rp::check_launch(fn);
 }
 
 }  // extern "C"

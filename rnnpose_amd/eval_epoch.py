@@ -19,6 +19,7 @@ on any number of ranks; `data_io` reads the reference's on-disk formats the day 
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -51,13 +52,14 @@ class EvalItem:
     class_name: str
     image: torch.Tensor          # (3,H,W) observed image
     K: np.ndarray                # (3,3)
-    pose_init: np.ndarray        # (4,4) initial pose (PoseCNN / PVNet in the reference)
+    pose_init: np.ndarray        # (4,4) initial pose (PoseCNN / PVNet in the reference); None: HipEpoch(init=...) finds one inside `bbox`
     pose_gt: np.ndarray          # (4,4)
     geofea_2d: torch.Tensor      # (32,H,W) descriptors of the observed image (None: HipEpoch(desc2d=...) computes them)
     frame_id: int | None = None  # camera frame the object was seen in: items of one frame share `image` / `geofea_2d` (None: its own)
     depth: torch.Tensor | None = None   # (H,W) observed depth of the frame in the meshes' unit, 0 = missing; shared like `image` (BOP VSD)
     object_id: object = None     # views of ONE physical object from several calibrated cameras share it (None: the item is its own object)
     cam_from_rig: np.ndarray | None = None   # (4,4) camera-from-rig transform of the item's camera (None: the identity)
+    bbox: np.ndarray | None = None   # [xmin, ymin, xmax, ymax] inclusive pixels: the detector's box, where an item without pose_init is matched
 
 
 class PackedEpochMetrics:
@@ -177,8 +179,11 @@ class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
     def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None, occlusion=None,
-                 occlusion_margin=0.0, depth_term=None):
-        """depth_term (PoseRefiner's argument: True or a dict of depth_weight / depth_gate / edge_tol): `refine` and `refine_frame`
+                 occlusion_margin=0.0, depth_term=None, init=None):
+        """init: "descriptors" or a pose_init.DescriptorPoseInitializer -- items whose pose_init is None get their start from the frame's
+        descriptor map inside their `bbox` (2D-3D matches, P3P RANSAC, polish; `initial_poses`); the record of the
+        last such call is in `last_init_info`.  None (the default): every item must bring its pose_init, and nothing new runs.
+        depth_term (PoseRefiner's argument: True or a dict of depth_weight / depth_gate / edge_tol): `refine` and `refine_frame`
         hand the frames' observed depth (EvalItem.depth) to the refiner, whose LM steps then carry its 3-D residual; an item without
         depth raises ValueError.  The statistics of the last call are in `last_depth_stats`.
         occlusion="frame" (PoseRefiner's argument; occlusion_margin in the models' length unit): refine_frame masks the pixels of
@@ -202,6 +207,13 @@ class HipEpoch:
         self.refiner = refiner if refiner is not None else \
             PoseRefiner(self.cfg, renderer=self.renderer, occlusion=occlusion, occlusion_margin=occlusion_margin,
                         depth_term=depth_term).to(self.device).eval()
+        if isinstance(init, str):
+            if init != "descriptors":
+                raise ValueError(f"init must be None, 'descriptors' or a DescriptorPoseInitializer, got {init!r}")
+            from .pose_init import DescriptorPoseInitializer
+            init = DescriptorPoseInitializer(models, device=self.device, pixel_center=getattr(self.renderer, "pixel_center", 0.5))
+        self.init = init
+        self.last_init_info = None        # initial_poses / refine / refine_frame: the record of the LAST such call (None: it initialised nothing)
         self.last_depth_stats = None
         self.last_rig_poses = None        # refine_frame with multi-view items: T_rig (n_groups,4,4) of the last call, groups in order of first appearance
         self._view_groups = {}            # ops.ViewGroups by (layout, transforms): the same rig keeps its device arrays, so captured graphs replay
@@ -234,12 +246,67 @@ class HipEpoch:
         else:
             g2 = torch.stack([it.geofea_2d for it in batch]).to(dev)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
-        T0 = torch.as_tensor(np.stack([it.pose_init for it in batch]).astype(np.float32)).to(dev)
+        T0 = self._start_poses(batch, g2, list(range(len(batch))), K)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=m.fea_3d.to(dev), Tj_gt=SE3Sequence(matrix=Tg[:, None]),
                            obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2, **self._observed_depth(batch))
         self.last_depth_stats = out.get("depth_stats")
         return out["Ti_pred"].G.reshape(-1, 4, 4)
+
+    def _start_poses(self, batch, g2, index, K, skip=(), caller_row=None):
+        """(B,4,4) start poses on the device: every item's pose_init; the items without one (rows in `skip` excepted: they get the
+        identity, their start comes from elsewhere) are initialised from the descriptor maps g2 (S,32,H,W) through `index`.
+        `last_init_info` becomes the record of this call -- its arrays in ascending order of `rows`, the rows of the CALLER's batch
+        (caller_row[j] = the caller's row of item j, where the batch was regrouped) -- or None when nothing was initialised."""
+        dev = self.device
+        self.last_init_info = None
+        need = [j for j, it in enumerate(batch) if it.pose_init is None and j not in skip]
+        bad = [j for j in need if self.init is None or batch[j].bbox is None]
+        if bad:
+            raise ValueError(f"items {bad} have no pose_init: they need a bbox and HipEpoch(init='descriptors' or a DescriptorPoseInitializer)")
+        eye = np.eye(4, dtype=np.float32)
+        T0 = torch.as_tensor(np.stack([eye if it.pose_init is None else np.asarray(it.pose_init, np.float32) for it in batch])).to(dev)
+        if need:
+            boxes = np.stack([np.asarray(batch[j].bbox).astype(np.int32).reshape(4) for j in need])
+            rows = torch.as_tensor(need, device=dev)
+            Ti, rec = self.init([batch[j].class_name for j in need], g2, [index[j] for j in need], K[rows].contiguous(), boxes)
+            T0[rows] = Ti
+            rows = np.asarray(need if caller_row is None else [caller_row[j] for j in need])
+            by_row = np.argsort(rows, kind="stable")
+            rec = {k: np.asarray(v)[by_row] for k, v in rec.items()}
+            rec["rows"] = rows[by_row]
+            self.last_init_info = rec
+        return T0
+
+    def _frames(self, batch):
+        """-> (first item of every distinct frame, the frame index of every item): items with the same non-None frame_id share a frame."""
+        src, index = {}, []
+        for j, it in enumerate(batch):
+            key = ("frame", it.frame_id) if it.frame_id is not None else ("item", j)
+            index.append(src.setdefault(key, (len(src), it))[0])
+        return [it for _, it in sorted(src.values(), key=lambda v: v[0])], index
+
+    def _frame_maps(self, firsts):
+        """-> images (S,3,H,W) and descriptor maps (S,32,H,W) of the frames, the latter computed where an item brings none."""
+        dev = self.device
+        image = torch.stack([it.image for it in firsts]).to(dev)
+        missing = [s for s, it in enumerate(firsts) if it.geofea_2d is None]
+        if missing and self.desc2d is None:
+            raise ValueError("items without geofea_2d need HipEpoch(desc2d=SuperPoint2D(...))")
+        fresh = iter(self.desc2d.descriptors(image[missing].float().contiguous())) if missing else iter(())
+        return image, torch.stack([next(fresh) if it.geofea_2d is None else it.geofea_2d.to(dev) for it in firsts])
+
+    def initial_poses(self, batch):
+        """(B,4,4) start poses of the items of one or several frames, in batch order: an item with a `bbox` is initialised from its
+        frame's descriptor map (whatever its pose_init), an item without one keeps its pose_init; neither raises ValueError.  The record
+        (count, n_inliers, final_cost, info, fallback per initialised row, and `rows`, their rows in `batch`, ascending) is in
+        `last_init_info`."""
+        if self.init is None:
+            raise ValueError("initial_poses needs HipEpoch(init='descriptors' or a DescriptorPoseInitializer)")
+        firsts, index = self._frames(batch)
+        _, g2 = self._frame_maps(firsts)
+        K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(self.device)
+        return self._start_poses([dataclasses.replace(it, pose_init=None) if it.bbox is not None else it for it in batch], g2, index, K)
 
     def _observed_depth(self, frames):
         """-> the refiner's depth= argument for these frames' items ({} when the depth term is off)."""
@@ -269,7 +336,11 @@ class HipEpoch:
         Multi-view: items with the same non-None `object_id` are views of one object from cameras with the
         camera-from-rig transforms `cam_from_rig`; they are refined as one group (PoseRefiner.forward(view_groups=)): one increment per
         object, the poses tied by the rig.  The pose_init of a group's FIRST item (in batch order) is its start, the others' are
-        ignored.  Items without object_id are groups of one.  `last_rig_poses` then holds T_rig per group."""
+        ignored.  Items without object_id are groups of one.  `last_rig_poses` then holds T_rig per group.
+        Items whose pose_init is None are initialised from their frame's descriptor map inside their `bbox` (HipEpoch(init=...),
+        DESIGN.md section 20) -- of a multi-view group only the first view; the record goes to `last_init_info` (`rows` = rows of `batch` as the
+        caller passed it; None when no item needed a start).  With every pose_init
+        given nothing new runs."""
         from .transformation import SE3Sequence
         dev = self.device
         order = vgroups = None
@@ -288,19 +359,12 @@ class HipEpoch:
                 if len(self._view_groups) >= 8:
                     self._view_groups.pop(next(iter(self._view_groups)))
                 vgroups = self._view_groups[key] = ops.ViewGroups(key[0], E, len(batch), dev)
-        src, index = {}, []
-        for j, it in enumerate(batch):
-            key = ("frame", it.frame_id) if it.frame_id is not None else ("item", j)
-            index.append(src.setdefault(key, (len(src), it))[0])
-        firsts = [it for _, it in sorted(src.values(), key=lambda v: v[0])]
-        image = torch.stack([it.image for it in firsts]).to(dev)
-        missing = [s for s, it in enumerate(firsts) if it.geofea_2d is None]
-        if missing and self.desc2d is None:
-            raise ValueError("items without geofea_2d need HipEpoch(desc2d=SuperPoint2D(...))")
-        fresh = iter(self.desc2d.descriptors(image[missing].float().contiguous())) if missing else iter(())
-        g2 = torch.stack([next(fresh) if it.geofea_2d is None else it.geofea_2d.to(dev) for it in firsts])
+        firsts, index = self._frames(batch)
+        image, g2 = self._frame_maps(firsts)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
-        T0 = torch.as_tensor(np.stack([it.pose_init for it in batch]).astype(np.float32)).to(dev)
+        # (multi-view: only the FIRST view of a group needs a start, the others are tied to it by the rig)
+        tied = () if order is None else {j for j in range(1, len(batch)) if gof[order[j]] == gof[order[j - 1]]}
+        T0 = self._start_poses(batch, g2, index, K, skip=tied, caller_row=order)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         names = [it.class_name for it in batch]
         fea = geo = None                                             # = the renderer's resident tables

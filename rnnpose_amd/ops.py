@@ -2050,3 +2050,144 @@ def raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K
             _ptr(pairs.occluder if P else None), P, margin, _ptr(own_keys), _ptr(ws), n, _ptr(visible), _ptr(occluder), _ptr(depth),
             _stream())
     return visible, occluder
+
+
+# ---- initial poses from 2D-3D descriptor matches (definitions in include/rnnpose_hip.h) -------------------------
+DESC_DIM = 32
+
+
+def _point_offsets(pt_off, total, max_points, device):
+    """-> (device int32 (B+1,), B, largest count).  A host sequence is checked here (ascending, inside [0, total]); a device tensor is
+    taken as it is, with max_points from the caller (the kernel gives count = 0 to an object whose range does not fit)."""
+    if isinstance(pt_off, torch.Tensor) and pt_off.is_cuda:
+        _i32_dev(pt_off, "pt_off")
+        if pt_off.dim() != 1 or pt_off.numel() < 2:
+            raise ValueError("desc_match: pt_off must hold B + 1 offsets")
+        if max_points is None:
+            raise ValueError("desc_match: a device pt_off needs max_points (the largest point count), as the rasteriser's max_faces")
+        return pt_off, pt_off.numel() - 1, int(max_points)
+    host = [int(v) for v in (pt_off.tolist() if hasattr(pt_off, "tolist") else pt_off)]
+    if len(host) < 2 or host[0] < 0 or host[-1] > total or any(b < a for a, b in zip(host, host[1:])):
+        raise ValueError(f"desc_match: pt_off must be B + 1 ascending offsets inside [0, {total}], got {host[:6]}")
+    largest = max(b - a for a, b in zip(host, host[1:]))
+    if largest < 1:
+        raise ValueError("desc_match: no object has a point")
+    return torch.tensor(host, dtype=torch.int32, device=device), len(host) - 1, largest if max_points is None else int(max_points)
+
+
+def desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=0.5, mutual=True, pixel_center=0.5, M=None,
+               max_points=None, out=None):
+    """2D-3D descriptor matcher (rnnpose_desc_match_f32).  desc3d (total,32) / points (total,3): the objects' point descriptors and
+    points back to back, object b = rows [pt_off[b], pt_off[b+1]) (pt_off: B+1 host integers, or a device int32 tensor with
+    max_points=); desc2d (S,32,H,W); src_index: an ops.SourceIndex, B integers or None (object b reads desc2d[b]); bbox (B,4) int32
+    [xmin, ymin, xmax, ymax] inclusive (ops.mask_bbox; a host sequence is copied), clamped to the image in the kernel; the box pixels
+    `step` apart from its (clamped) corner take part.  A point is a correspondence when its best pixel's similarity is >= min_sim
+    and, with mutual, that pixel's best point is the point itself.  M: output capacity per object (None: the largest point count,
+    so nothing is dropped).  out: (X, x, sim, point_idx, count) to write into.
+    -> X (B,M,3), x (B,M,2) pixel + pixel_center, sim (B,M), point_idx (B,M) int32, count (B) int32; rows >= count are NOT written
+    (fresh outputs are zero-filled).  Shapes, dtypes, devices and the index range are checked here, on the host (ValueError)."""
+    desc3d, points, desc2d = _chk(desc3d, "desc3d"), _chk(points, "points"), _chk(desc2d, "desc2d")
+    if desc3d.dim() != 2 or desc3d.shape[1] != DESC_DIM or desc3d.shape[0] < 1:
+        raise ValueError(f"desc_match: desc3d must be (points, {DESC_DIM}), got {tuple(desc3d.shape)}")
+    total = desc3d.shape[0]
+    if points.shape != (total, 3):
+        raise ValueError(f"desc_match: points must be ({total}, 3), got {tuple(points.shape)}")
+    if desc2d.dim() != 4 or desc2d.shape[1] != DESC_DIM or desc2d.numel() == 0:
+        raise ValueError(f"desc_match: desc2d must be (S, {DESC_DIM}, H, W), got {tuple(desc2d.shape)}")
+    if not (desc3d.device == points.device == desc2d.device):
+        raise ValueError("desc_match: desc3d, points and desc2d must live on one device")
+    S, _, H, W = desc2d.shape
+    dev = desc3d.device
+    pt_off, B, largest = _point_offsets(pt_off, total, max_points, dev)
+    if not 1 <= largest <= total:
+        raise ValueError(f"desc_match: max_points must lie in [1, {total}], got {largest}")
+    if src_index is None:
+        src_index = range(B)
+    if not isinstance(src_index, SourceIndex):
+        src_index = SourceIndex(src_index, S, dev)
+    if src_index.S != S or len(src_index) != B:
+        raise ValueError(f"desc_match: src_index covers {len(src_index)} objects of {src_index.S} sources; there are {B} objects, {S} sources")
+    if not isinstance(bbox, torch.Tensor) or not bbox.is_cuda:
+        bbox = torch.as_tensor(bbox, dtype=torch.int32).to(dev)
+    _i32_dev(bbox, "bbox")
+    if bbox.shape != (B, 4):
+        raise ValueError(f"desc_match: bbox must be ({B}, 4), got {tuple(bbox.shape)}")
+    step, M = int(step), int(largest if M is None else M)
+    min_sim = float(min_sim)
+    if step < 1 or M < 1 or min_sim != min_sim:
+        raise ValueError(f"desc_match: step >= 1, M >= 1 and a min_sim that is a number, got {step}, {M}, {min_sim}")
+    if out is None:
+        out = (torch.zeros(B, M, 3, device=dev, dtype=F32), torch.zeros(B, M, 2, device=dev, dtype=F32), torch.zeros(B, M, device=dev, dtype=F32),
+               torch.zeros(B, M, device=dev, dtype=torch.int32), torch.zeros(B, device=dev, dtype=torch.int32))
+    X, x, sim, pidx, count = out
+    for t, shape, dt, nm in ((X, (B, M, 3), F32, "X"), (x, (B, M, 2), F32, "x"), (sim, (B, M), F32, "sim"), (pidx, (B, M), torch.int32, "point_idx"),
+                             (count, (B,), torch.int32, "count")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"desc_match: out {nm} must be a contiguous {dt} GPU tensor of shape {shape}")
+    n = int(_lib.load().rnnpose_desc_match_workspace_bytes(total, B, H, W, step))
+    ws = torch.empty(n // 8, device=dev, dtype=torch.int64)
+    _launch("rnnpose_desc_match_f32", _ptr(desc3d), _ptr(points), _ptr(pt_off), total, largest, _ptr(desc2d), S, DESC_DIM, H, W,
+            _ptr(src_index.dev), _ptr(bbox), B, step, min_sim, int(bool(mutual)), float(pixel_center), M, _ptr(ws), n, _ptr(X), _ptr(x),
+            _ptr(sim), _ptr(pidx), _ptr(count), _stream())
+    return X, x, sim, pidx, count
+
+
+def random_words(rnd):
+    """Random 32-bit words as the int32 bit patterns the kernel reads as uint32: an integer tensor with values in [0, 2^32) (int64) or any
+    32-bit integer tensor."""
+    if not isinstance(rnd, torch.Tensor) or rnd.dtype.is_floating_point or rnd.dtype == torch.bool:
+        raise ValueError("rnd must be an integer tensor")
+    if rnd.dtype == torch.int64:
+        rnd = torch.where(rnd >= 2 ** 31, rnd - 2 ** 32, rnd).to(torch.int32)
+    elif rnd.dtype != torch.int32:
+        rnd = rnd.view(torch.int32) if rnd.element_size() == 4 else rnd.to(torch.int32)
+    return rnd.contiguous()
+
+
+def pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, T=None):
+    """P3P RANSAC with MSAC scoring and a Gauss-Newton polish, fp64 on the device (rnnpose_pnp_ransac_f64).  X (B,M,3), x (B,M,2),
+    count (B) int32: the matcher's outputs; K (3,3) or (B,3,3); rnd (B,Hyp,3) random 32-bit words (ops.random_words): hypothesis h of
+    object b samples the correspondences rnd[b,h,:] % count[b].  tau: inlier threshold in pixels.  T (B,4,4) fp32: written where
+    info == 0 and left as it is elsewhere (None: identities).
+    -> T (B,4,4), cost (B,Hyp) fp64, inliers (B,Hyp) int32, best (B) int32, inlier_mask (B,M) uint8, n_inliers (B) int32,
+       final_cost (B) fp64, info (B) int32 (0, or -1: too few correspondences / no candidate / singular polish).
+    Shapes, dtypes and devices are checked here, on the host (ValueError)."""
+    X, x, K = _chk(X, "X"), _chk(x, "x"), _chk(K, "K")
+    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"pnp_ransac: X must be (B,M,3), got {tuple(X.shape)}")
+    B, M = X.shape[0], X.shape[1]
+    if x.shape != (B, M, 2):
+        raise ValueError(f"pnp_ransac: x must be ({B},{M},2), got {tuple(x.shape)}")
+    _i32_dev(count, "count")
+    if count.shape != (B,):
+        raise ValueError(f"pnp_ransac: count must be ({B},), got {tuple(count.shape)}")
+    if K.shape == (3, 3):
+        K = K.expand(B, 3, 3).contiguous()
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"pnp_ransac: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
+    rnd = random_words(rnd)
+    if not rnd.is_cuda or rnd.dim() != 3 or rnd.shape[0] != B or rnd.shape[2] != 3 or rnd.shape[1] < 1:
+        raise ValueError(f"pnp_ransac: rnd must be a GPU tensor of shape ({B},Hyp,3), got {tuple(rnd.shape)} on {rnd.device}")
+    if not (X.device == x.device == count.device == K.device == rnd.device):
+        raise ValueError("pnp_ransac: all tensors must live on one device")
+    Hyp = rnd.shape[1]
+    tau, n_polish, min_count = float(tau), int(n_polish), int(min_count)
+    if not (tau > 0.0 and tau < float("inf")) or not 0 <= n_polish <= 64 or min_count < 4:
+        raise ValueError(f"pnp_ransac: tau > 0 and finite, n_polish in [0,64], min_count >= 4; got {tau}, {n_polish}, {min_count}")
+    dev = X.device
+    if T is None:
+        T = torch.eye(4, device=dev, dtype=F32).repeat(B, 1, 1)
+    elif not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == F32 and T.is_contiguous() and tuple(T.shape) == (B, 4, 4)):
+        raise ValueError(f"pnp_ransac: T must be a contiguous fp32 GPU tensor of shape ({B},4,4)")
+    n = int(_lib.load().rnnpose_pnp_ransac_workspace_bytes(B, Hyp))
+    ws = torch.empty(n // 8, device=dev, dtype=torch.int64)
+    cost = torch.empty(B, Hyp, device=dev, dtype=F64)
+    inliers = torch.empty(B, Hyp, device=dev, dtype=torch.int32)
+    best = torch.empty(B, device=dev, dtype=torch.int32)
+    mask = torch.zeros(B, M, device=dev, dtype=torch.uint8)
+    n_inl = torch.empty(B, device=dev, dtype=torch.int32)
+    fcost = torch.empty(B, device=dev, dtype=F64)
+    info = torch.empty(B, device=dev, dtype=torch.int32)
+    _launch("rnnpose_pnp_ransac_f64", _ptr(X), _ptr(x), _ptr(count), M, _ptr(K), _ptr(rnd), B, Hyp, tau, n_polish, min_count, _ptr(ws), n,
+            _ptr(T), _ptr(cost), _ptr(inliers), _ptr(best), _ptr(mask), _ptr(n_inl), _ptr(fcost), _ptr(info), _stream())
+    return T, cost, inliers, best, mask, n_inl, fcost, info

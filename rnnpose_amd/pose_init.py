@@ -1,0 +1,115 @@
+"""Initial poses from the picture: 2D-3D descriptor matches and P3P RANSAC.
+
+    init = DescriptorPoseInitializer(models, device)                 # models: {class: eval_epoch.ClassModel}
+    T0, rec = init(names, geofea_2d, image_index, K, bboxes)         # (B,4,4) and count / n_inliers / final_cost / info / fallback
+
+The descriptor map of a frame (`SuperPoint2D.descriptors`, `EvalItem.geofea_2d`) is matched against the point descriptors of each
+object's class (`ClassModel.geofea_3d`) inside the detector's box (`ops.desc_match`), and the matches go through a P3P RANSAC with an
+MSAC score and a Gauss-Newton polish on the device (`ops.pnp_ransac`).  Nothing here detects objects: the boxes are an input.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class DescriptorPoseInitializer:
+    # `tau` and `min_sim` are STARTING VALUES: no measurement of this project supports them ("not claimed").
+    def __init__(self, models, device="cuda", step=2, min_sim=0.5, mutual=True, hypotheses=1024, tau=4.0, n_polish=4, seed=0,
+                 pixel_center=0.5, min_count=4):
+        """hypotheses: log 0.01 / log(1 - w^3) of them give 99 % confidence at inlier ratio w; 1024 covers w >= 0.17 (not tuned).
+        seed: the random words of EVERY call come from a torch.Generator on the device re-seeded with it, so a call is a pure
+        function of its inputs."""
+        self.models = models
+        self.device = torch.device(device)
+        self.step, self.min_sim, self.mutual = int(step), float(min_sim), bool(mutual)
+        self.hypotheses, self.tau, self.n_polish, self.min_count = int(hypotheses), float(tau), int(n_polish), int(min_count)
+        self.seed, self.pixel_center = int(seed), float(pixel_center)
+        if self.hypotheses < 1:
+            raise ValueError("hypotheses must be >= 1")
+        self._class = {}        # class -> (descriptors (P,32), points (P,3)) on the device
+        self._tables = {}       # tuple of names -> (desc3d, points, offsets on the host, offsets on the device)
+        self._gen = None
+
+    def _tables_for(self, names):
+        key = tuple(names)
+        hit = self._tables.get(key)
+        if hit is None:
+            for n in set(names):
+                if n not in self._class:
+                    m = self.models[n]
+                    d = m.geofea_3d.reshape(-1, m.geofea_3d.shape[-1]).to(self.device, torch.float32).contiguous()
+                    p = torch.as_tensor(np.asarray(m.verts, np.float32)).to(self.device)
+                    if d.shape != (p.shape[0], ops.DESC_DIM):
+                        raise ValueError(f"class {n}: geofea_3d must hold {ops.DESC_DIM} channels for each of the {p.shape[0]} vertices")
+                    self._class[n] = (d, p)
+            off = [0]
+            for n in names:
+                off.append(off[-1] + self._class[n][1].shape[0])
+            if len(self._tables) >= 8:
+                self._tables.pop(next(iter(self._tables)))
+            hit = self._tables[key] = (torch.cat([self._class[n][0] for n in names]).contiguous(),
+                                       torch.cat([self._class[n][1] for n in names]).contiguous(), off,
+                                       torch.tensor(off, dtype=torch.int32, device=self.device))
+        return hit
+
+    def random_words(self, B):
+        """(B, hypotheses, 3) random 32-bit words (int64 values in [0, 2^32)) of a call with B objects."""
+        if self._gen is None:
+            self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(self.seed)
+        return torch.randint(0, 2 ** 32, (B, self.hypotheses, 3), generator=self._gen, device=self.device, dtype=torch.int64)
+
+    def match(self, names, geofea_2d, image_index, bboxes):
+        """The matcher alone -> X, x, sim, point_idx, count (ops.desc_match)."""
+        desc3d, points, off, off_dev = self._tables_for(names)
+        largest = max(b - a for a, b in zip(off, off[1:]))
+        if not isinstance(image_index, ops.SourceIndex):
+            image_index = ops.SourceIndex(range(len(names)) if image_index is None else image_index, geofea_2d.shape[0], self.device)
+        return ops.desc_match(desc3d, points, off_dev, geofea_2d, image_index, bboxes, self.step, self.min_sim, self.mutual, self.pixel_center,
+                              max_points=largest)
+
+    def fallback(self, name, K, bbox, size):
+        """The box-centre start of an object RANSAC gave no pose for: rotation = identity, t = K^-1 (box centre, 1) z with
+        z = f diameter / max(box width, box height), f = (fx + fy) / 2.  The box is clamped to the image; an empty box counts as the
+        whole image."""
+        H, W = size
+        x0, y0, x1, y1 = max(int(bbox[0]), 0), max(int(bbox[1]), 0), min(int(bbox[2]), W - 1), min(int(bbox[3]), H - 1)
+        if x1 < x0 or y1 < y0:
+            x0, y0, x1, y1 = 0, 0, W - 1, H - 1
+        K = np.asarray(K, np.float64)
+        z = 0.5 * (K[0, 0] + K[1, 1]) * float(self.models[name].diameter) / max(x1 - x0 + 1, y1 - y0 + 1)
+        T = np.eye(4)
+        T[:3, 3] = np.linalg.solve(K, np.array([0.5 * (x0 + x1) + self.pixel_center, 0.5 * (y0 + y1) + self.pixel_center, 1.0])) * z
+        return T.astype(np.float32)
+
+    def __call__(self, names, geofea_2d, image_index, K, bboxes):
+        """names: B class names; geofea_2d (S,32,H,W) on the device; image_index: B integers (which map every object reads), an
+        ops.SourceIndex or None (object b reads map b); K (3,3) or (B,3,3); bboxes (B,4) [xmin, ymin, xmax, ymax] inclusive pixels
+        (a device int32 tensor as ops.mask_bbox gives, or host values).
+        -> T0 (B,4,4) fp32 on the device and a record of host arrays: count (matches), n_inliers, final_cost, info (0 = RANSAC pose,
+        -1 = none) and fallback (True where the box-centre start was taken instead).  Never raises for a pose it cannot find."""
+        B = len(names)
+        if B < 1:
+            raise ValueError("no objects")
+        geofea_2d = ops._chk(geofea_2d, "geofea_2d")
+        Kt = torch.as_tensor(np.asarray(K, np.float32)) if not isinstance(K, torch.Tensor) else K
+        Kt = Kt.to(self.device, torch.float32)
+        if Kt.shape == (3, 3):
+            Kt = Kt.expand(B, 3, 3)
+        Kt = Kt.contiguous()
+        if not isinstance(bboxes, torch.Tensor):
+            bboxes = torch.as_tensor(np.asarray(bboxes).astype(np.int32).reshape(B, 4))
+        bboxes = bboxes.to(self.device, torch.int32).contiguous()
+        X, x, _, _, count = self.match(names, geofea_2d, image_index, bboxes)
+        T, _, _, _, _, n_inl, fcost, info = ops.pnp_ransac(X, x, count, Kt, self.random_words(B), self.tau, self.n_polish, self.min_count)
+        rec = dict(count=count.cpu().numpy(), n_inliers=n_inl.cpu().numpy(), final_cost=fcost.cpu().numpy(), info=info.cpu().numpy())
+        rec["fallback"] = rec["info"] != 0
+        if rec["fallback"].any():
+            Kh, bh = Kt.cpu().numpy(), bboxes.cpu().numpy()
+            rows = np.nonzero(rec["fallback"])[0]
+            fb = np.stack([self.fallback(names[j], Kh[j], bh[j], geofea_2d.shape[-2:]) for j in rows])
+            T[torch.as_tensor(rows, device=self.device)] = torch.as_tensor(fb).to(self.device)
+        return T, rec

@@ -35,6 +35,8 @@ _SCHEMAS = {
     "lm_step": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi)",
     "lm_step_rgbd": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor obs_depth, Tensor theta, Tensor K_obs, Tensor? src_index=None, float depth_weight=1.0, float depth_gate=0.05, float edge_tol=0.02, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor depth_stats)",
     "lm_step_views": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor group_start, Tensor cam_from_rig, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor Hg, Tensor bg)",
+    "desc_match": "(Tensor desc3d, Tensor points, Tensor pt_off, Tensor desc2d, Tensor src_index, Tensor bbox, int step=2, float min_sim=0.5, bool mutual=True, float pixel_center=0.5, int M=0) -> (Tensor X, Tensor x, Tensor sim, Tensor point_idx, Tensor count)",
+    "pnp_ransac": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4) -> (Tensor T, Tensor cost, Tensor inliers, Tensor best, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info)",
 }
 
 
@@ -126,7 +128,31 @@ def _bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus
     return ops.bop_vsd(depth_est, depth_gt, depth_obs, src_index, K, diameter, delta, taus)
 
 
+def _desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=0.5, mutual=True, pixel_center=0.5, M=0):
+    """pt_off (B+1,) and src_index (B,): integer tensors, checked on the host (ValueError) before anything is launched.  M = 0: the total
+    number of points (a capacity no object exceeds, and one the fake kernel knows too)."""
+    return ops.desc_match(desc3d, points, pt_off.detach().cpu().tolist(), desc2d, src_index, bbox.to(torch.int32).contiguous(), step, min_sim,
+                          mutual, pixel_center, M if M > 0 else points.shape[0])
+
+
+def _pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4):
+    return ops.pnp_ransac(X, x, count.to(torch.int32).contiguous(), K, rnd, tau, n_polish, min_count)
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
+def _f_desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=0.5, mutual=True, pixel_center=0.5, M=0):
+    B, M = bbox.shape[0], (M if M > 0 else points.shape[0])
+    e = lambda shape, dt: desc3d.new_empty(shape, dtype=dt)
+    return e((B, M, 3), torch.float32), e((B, M, 2), torch.float32), e((B, M), torch.float32), e((B, M), torch.int32), e((B,), torch.int32)
+
+
+def _f_pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4):
+    B, M, Hyp = X.shape[0], X.shape[1], rnd.shape[1]
+    e = lambda shape, dt: X.new_empty(shape, dtype=dt)
+    return (e((B, 4, 4), torch.float32), e((B, Hyp), torch.float64), e((B, Hyp), torch.int32), e((B,), torch.int32), e((B, M), torch.uint8),
+            e((B,), torch.int32), e((B,), torch.float64), e((B,), torch.int32))
+
+
 def _f_corr_pyramid(fmap1, fmap2, levels=4):
     B, _, h, w = fmap1.shape
     return [fmap1.new_empty((B * h * w, 1, hl, wl), dtype=torch.float32) for hl, wl in _level_sizes(h, w, levels)]
@@ -208,7 +234,8 @@ def register():
              "lm_solve_update": (_lm_solve_update, _f_lm_solve_update), "lm_step": (_lm_step, _f_lm_step),
              "lm_step_rgbd": (_lm_step_rgbd, _f_lm_step_rgbd), "lm_step_views": (_lm_step_views, _f_lm_step_views),
              "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
-             "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd)}
+             "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd),
+             "desc_match": (_desc_match, _f_desc_match), "pnp_ransac": (_pnp_ransac, _f_pnp_ransac)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

@@ -1,0 +1,33 @@
+"""The pose initialiser's kernels (csrc/desc_match.cuh, csrc/pnp.cuh through the entry points in csrc/eval_metrics.hip) EXECUTED ON THE
+HOST (tests/host_exec/, see tests/test_kernels_on_host.py) in the `-m "not gpu"` tier: the matcher, P3P and RANSAC tests of
+tests/test_gpu_pose_init.py, UNMODIFIED, in a subprocess under the plugin tests/host_exec/pytest_hostexec.py.  Left to the GPU: the
+end-to-end test (it renders, refines and draws its random words on the device) and the dispatcher test (the host tensors are CPU tensors)."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "host_exec"))
+
+SELECT_K = "not end_to_end and not torch_ops"
+EXPECTED = 3 * 4 * 3 + 1 + 1 + 1 + 1 + 1 + 1 + 1      # matcher grid, duplicates / zeros / capacity, reruns / batch, bad arguments, P3P, RANSAC, edge cases, bad arguments
+
+
+def test_pose_init_gpu_tests_pass_on_the_host_executed_kernels(tmp_path_factory):
+    import build_host
+    try:
+        build_host.clang()
+    except RuntimeError as e:
+        pytest.skip(str(e))
+    lib = build_host.build(str(tmp_path_factory.mktemp("host_exec")))
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "tests") + os.pathsep + ROOT, HOSTEXEC_DIR=os.path.dirname(lib))
+    cmd = [sys.executable, "-m", "pytest", "-p", "host_exec.pytest_hostexec", "-m", "gpu", "-q", "-p", "no:cacheprovider", "-k", SELECT_K,
+           "tests/test_gpu_pose_init.py"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500)
+    tail = r.stdout[-3000:]
+    m = re.search(r"(\d+) passed", tail)
+    assert r.returncode == 0 and m and " failed" not in tail.splitlines()[-1], tail
+    assert int(m.group(1)) == EXPECTED, tail

@@ -32,7 +32,15 @@ tests/bop_ref.py on the same inputs.  Nothing is compared against a threshold.
 measures the depth term of the LM step (PoseRefiner(depth_term=True)): `refine_frame` without (the parent's
 behaviour) and with the term on the frame's observed depth, alternating inside every run; and the step alone at the 240 x 240 crops of the
 initial poses -- ops.lm_step against ops.lm_step_rgbd on the same inputs, 50 launches per timed window.  Nothing is compared against a
-threshold."""
+threshold.
+
+    python tools/scene_bench.py --init [--out profiles/scene_bench_init.json]
+
+times the pose initialiser on the frame, boxes = ops.mask_bbox of every object's depth at its ground-truth pose
+padded by 8 px: the matcher alone (ops.desc_match), RANSAC plus polish alone on its matches (ops.pnp_ransac, random words drawn
+beforehand), `HipEpoch.initial_poses` (both, the random words, the copy back of the record), `refine_frame` on items without a pose, and
+`refine_frame` with the poses given next to it.  The ADD of the initial poses against the ground truth is recorded.  Nothing is compared
+against a threshold."""
 from __future__ import annotations
 
 import argparse
@@ -293,6 +301,59 @@ def bop_bench(a, models, hip, items, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def init_bench(a, models, cfg, net, hip, items, given, size, cover):
+    """--init: the pose initialiser on the frame's rendered descriptor map"""
+    import dataclasses
+    H, W = size
+    n = len(items)
+    hip_i = ee.HipEpoch(models, cfg=cfg, desc2d=net, init="descriptors")
+    hip_i.refiner.load_state_dict(hip.refiner.state_dict())
+    ini = hip_i.init
+    names = [it.class_name for it in items]
+    Tg = torch.as_tensor(np.stack([it.pose_gt for it in items]).astype(np.float32)).cuda()
+    K = torch.as_tensor(np.stack([it.K for it in items]).astype(np.float32)).cuda()
+    boxes_dev = ops.mask_bbox(hip_i.renderer.render_zbuf(names, Tg, K, (H, W)).float().contiguous())
+    boxes = boxes_dev.cpu().numpy() + np.array([-8, -8, 8, 8], np.int32)
+    boxes_dev = torch.as_tensor(boxes).cuda()
+    boxed = [dataclasses.replace(it, bbox=bb) for it, bb in zip(given, boxes)]
+    bare = [dataclasses.replace(it, pose_init=None) for it in boxed]
+    g2 = given[0].geofea_2d[None].float().contiguous()
+    idx = ops.SourceIndex([0] * n, 1, "cuda")
+    X, x, sim, pidx, count = ini.match(names, g2, idx, boxes_dev)
+    words = ops.random_words(ini.random_words(n))
+    T0 = hip_i.initial_poses(bare)
+    rec = hip_i.last_init_info
+    fed = [dataclasses.replace(it, pose_init=T0[j].cpu().numpy(), bbox=None) for j, it in enumerate(boxed)]
+    times = time_alternately({"matcher": lambda: ini.match(names, g2, idx, boxes_dev),
+                              "ransac_and_polish": lambda: ops.pnp_ransac(X, x, count, K, words, ini.tau, ini.n_polish, ini.min_count),
+                              "initial_poses": lambda: hip_i.initial_poses(bare),
+                              "refine_frame_without_poses": lambda: hip_i.refine_frame(bare),
+                              "refine_frame_poses_given": lambda: hip_i.refine_frame(fed)}, a.runs, a.warmup)
+    add = []
+    for j, it in enumerate(items):
+        v = models[it.class_name].verts.astype(np.float64)
+        T = T0[j].cpu().numpy().astype(np.float64)
+        g = np.asarray(it.pose_gt, np.float64)
+        add.append(float(np.linalg.norm((v @ T[:3, :3].T + T[:3, 3]) - (v @ g[:3, :3].T + g[:3, 3]), axis=1).mean() / models[it.class_name].diameter))
+    area = [int(max(0, min(b[2], W - 1) - max(b[0], 0) + 1) * max(0, min(b[3], H - 1) - max(b[1], 0) + 1)) for b in boxes]
+    med = lambda k: times[k]["median_ms"]
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=[H, W], crop=list(cfg.zoom_crop_size), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               verts_per_object=int(next(iter(models.values())).verts.shape[0]), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               step=ini.step, min_sim=ini.min_sim, mutual=ini.mutual, hypotheses=ini.hypotheses, tau=ini.tau, n_polish=ini.n_polish,
+               box_pixels=area, matches=[int(c) for c in rec["count"]], inliers=[int(c) for c in rec["n_inliers"]], info=[int(c) for c in rec["info"]],
+               add_over_diameter=add, device_ms=times,
+               note="matcher = ops.desc_match (clear, forward, backward, select: plain fp32 VALU form, the only form built); ransac_and_polish = "
+                    "ops.pnp_ransac on the matcher's outputs with the random words drawn beforehand; initial_poses = both + the words + the copy "
+                    "back of the record; the descriptor map is RENDERED from the models' own vertex descriptors (no trained weights); boxes = "
+                    "mask_bbox of the ground-truth depth + 8 px; nothing is compared against a threshold")
+    print(f"matcher {med('matcher'):.3f} ms   RANSAC + polish {med('ransac_and_polish'):.3f} ms   initial_poses {med('initial_poses'):.3f} ms")
+    print(f"refine_frame without poses {med('refine_frame_without_poses'):.2f} ms   with poses given {med('refine_frame_poses_given'):.2f} ms")
+    print(f"  matches {res['matches']}  inliers {res['inliers']}  ADD / diameter {[round(v, 4) for v in add]}")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=8)
@@ -305,6 +366,7 @@ def main():
     ap.add_argument("--bop", action="store_true", help="time the BOP pose-error functions of the frame instead (see above)")
     ap.add_argument("--depth", action="store_true", help="measure the depth term of the LM step instead (see above)")
     ap.add_argument("--views", action="store_true", help="measure multi-view refinement instead: 4 objects x 2 cameras, grouped against ungrouped")
+    ap.add_argument("--init", action="store_true", help="time the pose initialiser (descriptor matcher + P3P RANSAC) on the frame instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -328,6 +390,8 @@ def main():
         return occlusion_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
     if a.depth:
         return depth_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
+    if a.init:
+        return init_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
     per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
     whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
