@@ -809,6 +809,32 @@ int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int
                            int* inliers, int* best, unsigned char* inlier_mask, int* n_inliers, double* final_cost, int* info,
                            rnnpose_stream_t stream);
 
+/* ---- Pose confidence: render-and-compare score of a pose against its frame (no counterpart in the reference) ----
+ * rend_depth (B,h,w) fp32 and rend_desc (B,D,h,w) fp32, D = 32: the object's z-buffer and its per-vertex descriptors rendered under
+ *   the pose into a WINDOW of the frame, the principal point shifted by the window's integer corner; window (B,2) device int32
+ *   (x0, y0), any sign; desc2d (S,D,H,W) fp32 the frames' descriptor maps; depth_obs (S,H,W) fp32 the observed depth, or NULL;
+ *   src_index (B) device int32.  Window pixel (x, y) of pose b IS frame pixel (u, v) = (x0 + x, y0 + y) of frame src_index[b]: nothing
+ *   is resampled.  All arithmetic fp64 on values converted from fp32, without fma contraction.
+ *   Per window pixel: RENDERED iff z = rend_depth is finite and > 0.  A rendered pixel with (u, v) outside [0,W) x [0,H) is OUTSIDE.
+ *   An inside pixel, with d = depth_obs[s,v,u] valid iff finite and > 0 and dd = d - z: dd < -depth_tol OCCLUDED; |dd| <= depth_tol
+ *   CONSISTENT; dd > depth_tol VIOLATED; d invalid or depth_obs NULL: HOLE.  Inside pixels that are not occluded are compared: a (the D
+ *   channels of rend_desc) against g (those of desc2d); a non-finite channel on either side makes the pixel BAD, else
+ *   cos = (sum_k a_k g_k) / (max(|a|, 1e-12) max(|g|, 1e-12)) -- a zero vector gives 0 and counts.
+ *   stats (B,10) fp64 = [n_rend, n_out, n_occ, n_cons, n_viol, n_hole, n_desc, sum cos, sum |dd| over consistent, n_bad], with
+ *   n_rend = n_out + n_occ + n_cons + n_viol + n_hole and n_desc + n_bad = n_cons + n_viol + n_hole.
+ *   score (B) fp64 = max(sum cos / n_desc, 0) * n_cons / (n_cons + n_viol)   (the second factor 1 when its denominator is 0; score 0
+ *   when n_desc = 0).  A src_index outside [0, S) gives a zero row and score 0 -- THE CALLER checks the range on the host
+ *   (rnnpose_amd.ops.pose_score does).
+ *   workspace: one row of 10 doubles per 256-pixel chunk of every window (rnnpose_pose_score_workspace_bytes, 8-byte aligned).
+ *   Two launches: partial rows (a lane per window pixel, flat grid over B x chunks, fixed xor butterfly), then their sum per pose in
+ *   ascending chunk order.  No atomics: bit-identical from run to run, and a pose alone gives the bits it gives in a batch.
+ *   A null pointer other than depth_obs, D != 32, B / S / h / w / H / W < 1, a depth_tol that is negative or not finite or a short
+ *   workspace return 1 and launch nothing; no allocation, no synchronisation. */
+size_t rnnpose_pose_score_workspace_bytes(int B, int h, int w);
+int rnnpose_pose_score_f64(const float* rend_depth, const float* rend_desc, const int* window, const float* desc2d, const float* depth_obs,
+                           const int* src_index, int B, int S, int D, int h, int w, int H, int W, double depth_tol, void* workspace,
+                           size_t workspace_bytes, double* stats, double* score, rnnpose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@
 // points are at the end of this file, so that the host-executed test tier (which builds a fixed list of sources) carries them too.
 #include "desc_match.cuh"
 #include "pnp.cuh"
+// the pose confidence, placed the same way
+#include "pose_score.cuh"
 
 namespace {
 
@@ -498,6 +500,29 @@ int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int
   hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
   hipLaunchKernelGGL(pnp::pnp_polish_kernel, dim3(B), dim3(64), 0, st, X, x, count, M, K, B, Hyp, tau, n_polish, rec, cost, T, best, inlier_mask,
                      n_inliers, final_cost, info);
+  return rp::check_launch(fn);
+}
+
+// ---- pose confidence: render-and-compare score of a pose against its frame (csrc/pose_score.cuh) ----------------------------------------
+size_t rnnpose_pose_score_workspace_bytes(int B, int h, int w) { return ps::workspace_bytes(B, h, w); }
+
+int rnnpose_pose_score_f64(const float* rend_depth, const float* rend_desc, const int* window, const float* desc2d, const float* depth_obs,
+                           const int* src_index, int B, int S, int D, int h, int w, int H, int W, double depth_tol, void* workspace,
+                           size_t workspace_bytes, double* stats, double* score, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_pose_score_f64";
+  RP_REQUIRE(rend_depth && rend_desc && window && desc2d && src_index && workspace && stats && score, fn, "null pointer");
+  RP_REQUIRE(D == ps::kD, fn, "D must be 32");
+  RP_REQUIRE(B > 0 && S > 0 && h > 0 && w > 0 && H > 0 && W > 0, fn, "bad size");
+  RP_REQUIRE(static_cast<long long>(H) * W < (1ll << 31) && ps::workspace_bytes(B, h, w) > 0, fn, "bad size (too large)");
+  RP_REQUIRE(depth_tol >= 0.0 && depth_tol - depth_tol == 0.0, fn, "depth_tol must be non-negative and finite");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= ps::workspace_bytes(B, h, w), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  const int nchunk = ps::chunks(h, w);
+  double* partial = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(ps::ps_partial_kernel, dim3(B * nchunk), dim3(256), 0, st, rend_depth, rend_desc, window, desc2d, depth_obs, src_index, S, h,
+                     w, H, W, nchunk, depth_tol, partial);
+  hipLaunchKernelGGL(ps::ps_final_kernel, dim3(B), dim3(64), 0, st, static_cast<const double*>(partial), nchunk, stats, score);
   return rp::check_launch(fn);
 }
 

@@ -179,8 +179,12 @@ class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
     def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None, occlusion=None,
-                 occlusion_margin=0.0, depth_term=None, init=None):
-        """init: "descriptors" or a pose_init.DescriptorPoseInitializer -- items whose pose_init is None get their start from the frame's
+                 occlusion_margin=0.0, depth_term=None, init=None, score=False):
+        """score: True or a pose_score.PoseScorer -- `refine` and `refine_frame` also score the poses they return against their frames
+        (the object's descriptors and depth rendered under the pose, compared with the frame's descriptor map and,
+        where every item has one, its observed depth) and leave the scores in `last_scores`, the record in `last_score_info`.  False (the
+        default): nothing new runs and `last_scores` stays None; `score_poses` / `select_poses` work either way.
+        init: "descriptors" or a pose_init.DescriptorPoseInitializer -- items whose pose_init is None get their start from the frame's
         descriptor map inside their `bbox` (2D-3D matches, P3P RANSAC, polish; `initial_poses`); the record of the
         last such call is in `last_init_info`.  None (the default): every item must bring its pose_init, and nothing new runs.
         depth_term (PoseRefiner's argument: True or a dict of depth_weight / depth_gate / edge_tol): `refine` and `refine_frame`
@@ -214,6 +218,13 @@ class HipEpoch:
             init = DescriptorPoseInitializer(models, device=self.device, pixel_center=getattr(self.renderer, "pixel_center", 0.5))
         self.init = init
         self.last_init_info = None        # initial_poses / refine / refine_frame: the record of the LAST such call (None: it initialised nothing)
+        if score is True:
+            from .pose_score import PoseScorer
+            score = PoseScorer(self.renderer, models, device=self.device)
+        self.scorer = score or None       # refine / refine_frame score their results with it; None: they do not
+        self._default_scorer = None       # score_poses / select_poses without one: made on their first call
+        self.last_scores = None           # refine / refine_frame with a scorer: (B) fp64 scores of the poses they returned, in batch order
+        self.last_score_info = None       # the record of the LAST scoring call (PoseScorer.__call__)
         self.last_depth_stats = None
         self.last_rig_poses = None        # refine_frame with multi-view items: T_rig (n_groups,4,4) of the last call, groups in order of first appearance
         self._view_groups = {}            # ops.ViewGroups by (layout, transforms): the same rig keeps its device arrays, so captured graphs replay
@@ -251,7 +262,9 @@ class HipEpoch:
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=m.fea_3d.to(dev), Tj_gt=SE3Sequence(matrix=Tg[:, None]),
                            obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2, **self._observed_depth(batch))
         self.last_depth_stats = out.get("depth_stats")
-        return out["Ti_pred"].G.reshape(-1, 4, 4)
+        poses = out["Ti_pred"].G.reshape(-1, 4, 4)
+        self.last_scores = None if self.scorer is None else self.score_poses(batch, poses, scorer=self.scorer)
+        return poses
 
     def _start_poses(self, batch, g2, index, K, skip=(), caller_row=None):
         """(B,4,4) start poses on the device: every item's pose_init; the items without one (rows in `skip` excepted: they get the
@@ -286,11 +299,12 @@ class HipEpoch:
             index.append(src.setdefault(key, (len(src), it))[0])
         return [it for _, it in sorted(src.values(), key=lambda v: v[0])], index
 
-    def _frame_maps(self, firsts):
-        """-> images (S,3,H,W) and descriptor maps (S,32,H,W) of the frames, the latter computed where an item brings none."""
+    def _frame_maps(self, firsts, want_image=True):
+        """-> images (S,3,H,W) and descriptor maps (S,32,H,W) of the frames, the latter computed where an item brings none.
+        want_image=False: the images are stacked only if a descriptor map has to be computed from them (None otherwise)."""
         dev = self.device
-        image = torch.stack([it.image for it in firsts]).to(dev)
         missing = [s for s, it in enumerate(firsts) if it.geofea_2d is None]
+        image = torch.stack([it.image for it in firsts]).to(dev) if want_image or missing else None
         if missing and self.desc2d is None:
             raise ValueError("items without geofea_2d need HipEpoch(desc2d=SuperPoint2D(...))")
         fresh = iter(self.desc2d.descriptors(image[missing].float().contiguous())) if missing else iter(())
@@ -307,6 +321,48 @@ class HipEpoch:
         _, g2 = self._frame_maps(firsts)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(self.device)
         return self._start_poses([dataclasses.replace(it, pose_init=None) if it.bbox is not None else it for it in batch], g2, index, K)
+
+    def score_poses(self, batch, poses, scorer=None):
+        """Render-and-compare confidence of the poses `poses` (B,4,4) of the items of `batch` (any classes, one or several camera
+        frames) -> (B) fp64 scores on the device, in batch order; `last_score_info` becomes the record
+        (PoseScorer.__call__).  Every frame's descriptor map is held once, as refine_frame holds it, and every item reads its frame's
+        through a source index; the observed depth (EvalItem.depth) is used where EVERY item has one.  No pose_gt is read.
+        scorer: a pose_score.PoseScorer (None: the one of HipEpoch(score=...), or a default one)."""
+        return self._score(batch, poses, 1, scorer)
+
+    def select_poses(self, batch, candidates):
+        """candidates (B,N,4,4): N pose hypotheses for every item of `batch`; all B * N are scored in ONE call.
+        -> (poses (B,4,4) the best hypothesis of every item, index (B) int64 which one, scores (B,N) fp64), on the device; equal scores
+        go to the LOWEST index.  `last_score_info` holds the record with its per-pose arrays reshaped to (B,N,...)."""
+        cand = candidates if torch.is_tensor(candidates) else torch.as_tensor(np.asarray(candidates, np.float32))
+        cand = cand.to(self.device, torch.float32)
+        if cand.dim() != 4 or cand.shape[0] != len(batch) or cand.shape[1] < 1 or cand.shape[2:] != (4, 4):
+            raise ValueError(f"select_poses: candidates must be ({len(batch)},N,4,4), got {tuple(cand.shape)}")
+        B, N = cand.shape[:2]
+        scores = self._score(batch, cand.reshape(B * N, 4, 4), N, None).reshape(B, N)
+        self.last_score_info = {k: (np.asarray(v).reshape(B, N, *np.asarray(v).shape[1:]) if k != "window_size" else v)
+                                for k, v in self.last_score_info.items()}
+        index = torch.as_tensor(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)          # (numpy: the first maximum)
+        return cand[torch.arange(B, device=self.device), index], index, scores
+
+    def _score(self, batch, poses, reps, scorer):
+        """Scores of poses (B * reps,4,4): item j owns the rows [j reps, (j + 1) reps)."""
+        if scorer is None:
+            scorer = self.scorer
+        if scorer is None:
+            if self._default_scorer is None:
+                from .pose_score import PoseScorer
+                self._default_scorer = PoseScorer(self.renderer, self.models, device=self.device)
+            scorer = self._default_scorer
+        if len(batch) < 1 or len(poses) != len(batch) * reps:
+            raise ValueError(f"{len(poses)} poses for {len(batch)} items x {reps}")
+        firsts, index = self._frames(batch)
+        _, g2 = self._frame_maps(firsts, want_image=False)
+        depth = None if any(it.depth is None for it in firsts) else torch.stack([it.depth for it in firsts]).to(self.device).float().contiguous()
+        rows = [j for j in range(len(batch)) for _ in range(reps)]
+        K = np.stack([batch[j].K for j in rows]).astype(np.float32)
+        score, self.last_score_info = scorer([batch[j].class_name for j in rows], poses, K, g2.float().contiguous(), [index[j] for j in rows], depth)
+        return score
 
     def _observed_depth(self, frames):
         """-> the refiner's depth= argument for these frames' items ({} when the depth term is off)."""
@@ -344,6 +400,7 @@ class HipEpoch:
         from .transformation import SE3Sequence
         dev = self.device
         order = vgroups = None
+        given = batch                                                             # (the caller's order: the scores are taken in it)
         if any(it.object_id is not None or it.cam_from_rig is not None for it in batch):
             from . import ops
             gid = {}
@@ -377,13 +434,15 @@ class HipEpoch:
         self.last_depth_stats = out.get("depth_stats")
         self.last_rig_poses = out.get("T_rig")
         poses = out["Ti_pred"].G.reshape(-1, 4, 4)
-        if order is None:
-            return poses
-        back = torch.empty(len(order), dtype=torch.long)
-        back[torch.tensor(order)] = torch.arange(len(order))                      # the caller's order
-        if self.last_depth_stats is not None:
-            self.last_depth_stats = self.last_depth_stats[back.to(dev)]
-        return poses[back.to(dev)]
+        if order is not None:
+            back = torch.empty(len(order), dtype=torch.long)
+            back[torch.tensor(order)] = torch.arange(len(order))                  # the caller's order
+            if self.last_depth_stats is not None:
+                self.last_depth_stats = self.last_depth_stats[back.to(dev)]
+            poses = poses[back.to(dev)]
+        # (multi-view items are scored view by view, each in its own camera and against its own frame)
+        self.last_scores = None if self.scorer is None else self.score_poses(given, poses, scorer=self.scorer)
+        return poses
 
     def bop_metrics(self, batch, pose_pred, want_errors=False):
         """BOP recalls of the poses `pose_pred` (B,4,4) of the items of `batch` (any classes, one or several camera frames):

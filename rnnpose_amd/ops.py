@@ -2191,3 +2191,72 @@ def pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, T=None):
     _launch("rnnpose_pnp_ransac_f64", _ptr(X), _ptr(x), _ptr(count), M, _ptr(K), _ptr(rnd), B, Hyp, tau, n_polish, min_count, _ptr(ws), n,
             _ptr(T), _ptr(cost), _ptr(inliers), _ptr(best), _ptr(mask), _ptr(n_inl), _ptr(fcost), _ptr(info), _stream())
     return T, cost, inliers, best, mask, n_inl, fcost, info
+
+
+# ---- pose confidence: render-and-compare score of a pose against its frame (definitions in include/rnnpose_hip.h) ----
+POSE_SCORE_COLUMNS = ("n_rend", "n_out", "n_occ", "n_cons", "n_viol", "n_hole", "n_desc", "sum_cos", "sum_abs_dd", "n_bad")
+_score_ws = {}
+
+
+def _strict(t, name, dtype, fn):
+    """The tensor as it is, or ValueError: nothing is converted or copied for the caller here."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        what = f"{t.dtype} on {t.device}, contiguous: {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{fn}: {name} must be a contiguous {dtype} GPU tensor, got {what}")
+    return t
+
+
+def pose_score(rend_depth, rend_desc, window, desc2d, src_index=None, depth_obs=None, depth_tol=0.015):
+    """Render-and-compare score of B poses (rnnpose_pose_score_f64).  rend_depth (B,h,w) or (B,1,h,w) and rend_desc (B,32,h,w) fp32:
+    every object's z-buffer and descriptors rendered into its window of the frame with the principal point shifted by the window's
+    corner; window (B,2) int32 (x0, y0) of any sign (a device tensor, or host values that are copied); desc2d (S,32,H,W) fp32;
+    src_index: an ops.SourceIndex, B integers or None (pose b reads frame b); depth_obs (S,H,W) fp32 or None; depth_tol >= 0, in
+    the depth maps' unit.
+    -> stats (B,10) fp64 in the order of POSE_SCORE_COLUMNS, score (B) fp64.
+    Shapes, dtypes, devices, contiguity and the index range are checked here, on the host (ValueError); nothing is converted.  The
+    workspace is cached per (device, B, h, w): calls of one shape must not overlap on different streams."""
+    fn = "pose_score"
+    rend_depth, rend_desc, desc2d = _strict(rend_depth, "rend_depth", F32, fn), _strict(rend_desc, "rend_desc", F32, fn), _strict(desc2d, "desc2d", F32, fn)
+    if rend_desc.dim() != 4 or rend_desc.shape[1] != DESC_DIM or rend_desc.numel() == 0:
+        raise ValueError(f"{fn}: rend_desc must be (B, {DESC_DIM}, h, w), got {tuple(rend_desc.shape)}")
+    B, _, h, w = rend_desc.shape
+    if tuple(rend_depth.shape) not in ((B, h, w), (B, 1, h, w)):
+        raise ValueError(f"{fn}: rend_depth must be ({B},{h},{w}) or ({B},1,{h},{w}), got {tuple(rend_depth.shape)}")
+    if desc2d.dim() != 4 or desc2d.shape[1] != DESC_DIM or desc2d.numel() == 0:
+        raise ValueError(f"{fn}: desc2d must be (S, {DESC_DIM}, H, W), got {tuple(desc2d.shape)}")
+    S, _, H, W = desc2d.shape
+    dev = rend_desc.device
+    if depth_obs is not None:
+        _strict(depth_obs, "depth_obs", F32, fn)
+        if tuple(depth_obs.shape) != (S, H, W):
+            raise ValueError(f"{fn}: depth_obs must be ({S},{H},{W}), got {tuple(depth_obs.shape)}")
+    if not isinstance(window, torch.Tensor) or not window.is_cuda:
+        window = torch.as_tensor(window, dtype=torch.int32).to(dev)
+    _strict(window, "window", torch.int32, fn)
+    if tuple(window.shape) != (B, 2):
+        raise ValueError(f"{fn}: window must be ({B}, 2), got {tuple(window.shape)}")
+    if src_index is None:
+        src_index = range(B)
+    if not isinstance(src_index, SourceIndex):
+        src_index = SourceIndex(src_index, S, dev)
+    if src_index.S != S or len(src_index) != B:
+        raise ValueError(f"{fn}: src_index covers {len(src_index)} poses of {src_index.S} frames; there are {B} poses, {S} frames")
+    if any(t.device != dev for t in (rend_depth, desc2d, window, src_index.dev) + (() if depth_obs is None else (depth_obs,))):
+        raise ValueError(f"{fn}: all tensors must live on one device")
+    depth_tol = float(depth_tol)
+    if not 0.0 <= depth_tol < float("inf"):
+        raise ValueError(f"{fn}: depth_tol must be non-negative and finite, got {depth_tol}")
+    n = int(_lib.load().rnnpose_pose_score_workspace_bytes(B, h, w))
+    if n == 0:
+        raise ValueError(f"{fn}: {B} windows of {h} x {w} pixels are more than one call takes")
+    key = (dev, B, h, w)
+    ws = _score_ws.get(key)
+    if ws is None:
+        if len(_score_ws) >= 8:
+            _score_ws.pop(next(iter(_score_ws)))
+        ws = _score_ws[key] = torch.empty(n // 8, device=dev, dtype=F64)
+    stats = torch.empty(B, len(POSE_SCORE_COLUMNS), device=dev, dtype=F64)
+    score = torch.empty(B, device=dev, dtype=F64)
+    _launch("rnnpose_pose_score_f64", _ptr(rend_depth), _ptr(rend_desc), _ptr(window), _ptr(desc2d), _ptr(depth_obs), _ptr(src_index.dev), B, S,
+            DESC_DIM, h, w, H, W, depth_tol, _ptr(ws), n, _ptr(stats), _ptr(score), _stream())
+    return stats, score

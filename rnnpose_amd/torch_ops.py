@@ -37,6 +37,7 @@ _SCHEMAS = {
     "lm_step_views": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor group_start, Tensor cam_from_rig, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor Hg, Tensor bg)",
     "desc_match": "(Tensor desc3d, Tensor points, Tensor pt_off, Tensor desc2d, Tensor src_index, Tensor bbox, int step=2, float min_sim=0.5, bool mutual=True, float pixel_center=0.5, int M=0) -> (Tensor X, Tensor x, Tensor sim, Tensor point_idx, Tensor count)",
     "pnp_ransac": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4) -> (Tensor T, Tensor cost, Tensor inliers, Tensor best, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info)",
+    "pose_score": "(Tensor rend_depth, Tensor rend_desc, Tensor window, Tensor desc2d, Tensor src_index, Tensor? depth_obs=None, float depth_tol=0.015) -> (Tensor stats, Tensor score)",
 }
 
 
@@ -139,7 +140,17 @@ def _pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4):
     return ops.pnp_ransac(X, x, count.to(torch.int32).contiguous(), K, rnd, tau, n_polish, min_count)
 
 
+def _pose_score(rend_depth, rend_desc, window, desc2d, src_index, depth_obs=None, depth_tol=0.015):
+    """src_index (B,): an integer tensor, checked on the host (ValueError) before anything is launched; window (B,2) any integer dtype."""
+    return ops.pose_score(rend_depth, rend_desc, window.to(torch.int32).contiguous(), desc2d, src_index, depth_obs, depth_tol)
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
+def _f_pose_score(rend_depth, rend_desc, window, desc2d, src_index, depth_obs=None, depth_tol=0.015):
+    B = rend_desc.shape[0]
+    return rend_desc.new_empty((B, len(ops.POSE_SCORE_COLUMNS)), dtype=torch.float64), rend_desc.new_empty((B,), dtype=torch.float64)
+
+
 def _f_desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=0.5, mutual=True, pixel_center=0.5, M=0):
     B, M = bbox.shape[0], (M if M > 0 else points.shape[0])
     e = lambda shape, dt: desc3d.new_empty(shape, dtype=dt)
@@ -235,7 +246,8 @@ def register():
              "lm_step_rgbd": (_lm_step_rgbd, _f_lm_step_rgbd), "lm_step_views": (_lm_step_views, _f_lm_step_views),
              "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
              "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd),
-             "desc_match": (_desc_match, _f_desc_match), "pnp_ransac": (_pnp_ransac, _f_pnp_ransac)}
+             "desc_match": (_desc_match, _f_desc_match), "pnp_ransac": (_pnp_ransac, _f_pnp_ransac),
+             "pose_score": (_pose_score, _f_pose_score)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

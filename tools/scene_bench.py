@@ -40,7 +40,14 @@ times the pose initialiser on the frame, boxes = ops.mask
 padded by 8 px: the matcher alone (ops.desc_match), RANSAC plus polish alone on its matches (ops.pnp_ransac, random words drawn
 beforehand), `HipEpoch.initial_poses` (both, the random words, the copy back of the record), `refine_frame` on items without a pose, and
 `refine_frame` with the poses given next to it.  The ADD of the initial poses against the ground truth is recorded.  Nothing is compared
-against a threshold."""
+against a threshold.
+
+    python tools/scene_bench.py --score [--out profiles/scene_bench_score.json]
+
+times the pose confidence on the frame and its observed depth, at the ground-truth poses: the kernel pair alone
+(ops.pose_score on tensors rendered beforehand, with and without the depth), `PoseScorer` as a whole (window, render, kernel pair, record),
+`HipEpoch.score_poses`, and `refine_frame` with `score=True` next to the plain one, alternating inside every run.  The scores at the
+ground-truth poses, at the initial poses and of the refined poses are recorded.  Nothing is compared against a threshold."""
 from __future__ import annotations
 
 import argparse
@@ -354,6 +361,57 @@ def init_bench(a, models, cfg, net, hip, items, given, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def score_bench(a, models, cfg, net, hip, items, given, size, cover):
+    """--score: the pose confidence on the frame, with its observed depth"""
+    n = len(items)
+    depth_dev = items[0].depth.cuda()
+    with_depth = [ee.EvalItem(it.class_name, it.image, it.K, it.pose_init, it.pose_gt, it.geofea_2d, frame_id=it.frame_id, depth=depth_dev)
+                  for it in given]
+    hip_on = ee.HipEpoch(models, cfg=cfg, desc2d=net, score=True)
+    hip_on.refiner.load_state_dict(hip.refiner.state_dict())
+    scorer = hip_on.scorer
+    names = [it.class_name for it in items]
+    Tg = np.stack([it.pose_gt for it in items]).astype(np.float32)
+    T0 = np.stack([it.pose_init for it in items]).astype(np.float32)
+    K = np.stack([it.K for it in items]).astype(np.float32)
+    g2, obs = given[0].geofea_2d[None].float().contiguous(), depth_dev[None].float().contiguous()
+    idx = ops.SourceIndex([0] * n, 1, "cuda")
+    rd, ra, win, _ = scorer.render(names, Tg, K, size)
+    at_gt = hip_on.score_poses(with_depth, Tg)
+    rec_gt = hip_on.last_score_info
+    at_init = hip_on.score_poses(with_depth, T0)
+    rec_init = hip_on.last_score_info
+    times = time_alternately({"kernel_pair": lambda: ops.pose_score(rd, ra, win, g2, idx, obs, scorer.depth_tol),
+                              "kernel_pair_without_depth": lambda: ops.pose_score(rd, ra, win, g2, idx, None, scorer.depth_tol),
+                              "pose_scorer": lambda: scorer(names, Tg, K, g2, idx, obs),
+                              "score_poses": lambda: hip_on.score_poses(with_depth, Tg),
+                              "refine_frame_score_off": lambda: hip.refine_frame(with_depth),
+                              "refine_frame_score_on": lambda: hip_on.refine_frame(with_depth)}, a.runs, a.warmup)
+    med = lambda k: times[k]["median_ms"]
+    added = med("refine_frame_score_on") - med("refine_frame_score_off")
+    lst = lambda v: [float(x) for x in v]
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=list(size), crop=list(cfg.zoom_crop_size), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               verts_per_object=int(next(iter(models.values())).verts.shape[0]), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               depth_tol=scorer.depth_tol, window=list(rec_gt["window_size"]), rendered_pixels=[int(v) for v in rec_gt["n_rend"]],
+               score_at_gt=lst(at_gt.cpu()), visible_fraction_at_gt=lst(rec_gt["visible_fraction"]), depth_factor_at_gt=lst(rec_gt["depth_factor"]),
+               score_at_initial_poses=lst(at_init.cpu()), visible_fraction_at_initial_poses=lst(rec_init["visible_fraction"]),
+               depth_factor_at_initial_poses=lst(rec_init["depth_factor"]), score_of_refined_poses=lst(hip_on.last_scores.cpu()),
+               device_ms=times, refine_frame_added_ms=added, refine_frame_added_share=added / med("refine_frame_score_off"),
+               note="kernel_pair = ops.pose_score (partial sums + final sum) on tensors rendered beforehand; pose_scorer = PoseScorer.__call__: the "
+                    "window on the host, one MeshRenderer call (32 descriptor channels + z-buffer), the kernel pair, the copy back of the record; "
+                    "score_poses = the same behind HipEpoch (frame maps stacked per call); refine_frame off / on alternate inside every run; the "
+                    "frame's descriptor map is RENDERED from the models' own vertex descriptors and the refiner's weights are random numbers, so "
+                    "the scores show the mechanism and no accuracy; nothing is compared against a threshold")
+    print(f"kernel pair {med('kernel_pair'):.4f} ms (without depth {med('kernel_pair_without_depth'):.4f})   PoseScorer {med('pose_scorer'):.3f} ms   "
+          f"score_poses {med('score_poses'):.3f} ms   window {res['window']}")
+    print(f"refine_frame score off {med('refine_frame_score_off'):.2f} ms   on {med('refine_frame_score_on'):.2f} ms   added {added:+.3f} ms "
+          f"({res['refine_frame_added_share']:+.2%})")
+    print(f"  score at gt {[round(v, 3) for v in res['score_at_gt']]}  at the initial poses {[round(v, 3) for v in res['score_at_initial_poses']]}")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=8)
@@ -367,6 +425,7 @@ def main():
     ap.add_argument("--depth", action="store_true", help="measure the depth term of the LM step instead (see above)")
     ap.add_argument("--views", action="store_true", help="measure multi-view refinement instead: 4 objects x 2 cameras, grouped against ungrouped")
     ap.add_argument("--init", action="store_true", help="time the pose initialiser (descriptor matcher + P3P RANSAC) on the frame instead (see above)")
+    ap.add_argument("--score", action="store_true", help="time the pose confidence (render-and-compare score) on the frame instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -392,6 +451,8 @@ def main():
         return depth_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
     if a.init:
         return init_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
+    if a.score:
+        return score_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
     per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
     whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
