@@ -809,6 +809,32 @@ int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int
                            int* inliers, int* best, unsigned char* inlier_mask, int* n_inliers, double* final_cost, int* info,
                            rnnpose_stream_t stream);
 
+/* ---- The K best DISTINCT RANSAC hypotheses, each polished (no counterpart in the reference) ----
+ * rnnpose_pnp_ransac_topk_f64: the inputs, `cost` and `inliers` of rnnpose_pnp_ransac_f64 (same solve and score launches), then:
+ *   EXTENT of object b: the axis-aligned box [lo, hi] of the X of its first cnt = clamp(count[b], 0, M) correspondences (fp64 on values
+ *   converted from fp32); diag = |hi - lo|, sep = sep_frac diag.  DISTANCE of two poses: d(P, Q) = max over the 8 box corners c of
+ *   |P c - Q c|, fp64 without fma contraction.
+ *   SELECTION (greedy): slot 0 is the cheapest hypothesis (the lowest h on a tie; exactly `best` of rnnpose_pnp_ransac_f64).  Slot
+ *   k >= 1 is the cheapest remaining hypothesis (the lowest h on a tie) with a finite cost, inliers[h] >= min_inliers and d > sep
+ *   between its candidate pose and the candidate pose of EVERY slot chosen before (the comparison must be true: a NaN distance is
+ *   never distinct).  min_inliers does not apply to slot 0.  It stops at Kt slots or when nothing remains: n_found (B) slots;
+ *   hyp (B,Kt) the hypothesis of every slot, -1 for k >= n_found.
+ *   POLISH of every slot as rnnpose_pnp_ransac_f64 polishes its one: T (B,Kt,4,4) fp32, inlier_mask (B,Kt,M) uint8 (rows < count
+ *   written), n_inliers (B,Kt), final_cost (B,Kt) fp64, info (B,Kt) = 0, or -1 with T[b][k] NOT written (mask 0, n_inliers 0,
+ *   final_cost +inf); slots k >= n_found have info -1.
+ *   dup_of (B,Kt): the lowest k' < k with info 0 whose POLISHED pose (fp64) is not farther than sep from slot k's (not d > sep), else
+ *   -1; -1 for a slot with info != 0.  Nothing is removed.
+ *   Slot 0 of every output is bit-identical to rnnpose_pnp_ransac_f64 on the same inputs, whatever Kt.  Five launches; no atomics,
+ *   fixed-order reductions: bit-identical from run to run, and an object alone gives the bits it gives in a batch.
+ *   workspace: the candidates, the polished poses, the extents and one flag per hypothesis (rnnpose_pnp_ransac_topk_workspace_bytes,
+ *   0 for a bad size; 8-byte aligned).  The argument errors of rnnpose_pnp_ransac_f64, Kt outside [1, 16], a sep_frac that is negative
+ *   or not finite, min_inliers < 0 or a short workspace return 1 and launch nothing; no allocation, no synchronisation. */
+size_t rnnpose_pnp_ransac_topk_workspace_bytes(int B, int Hyp, int Kt);
+int rnnpose_pnp_ransac_topk_f64(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
+                                double tau, int n_polish, int min_count, int Kt, double sep_frac, int min_inliers, void* workspace,
+                                size_t workspace_bytes, float* T, double* cost, int* inliers, int* hyp, unsigned char* inlier_mask,
+                                int* n_inliers, double* final_cost, int* info, int* dup_of, int* n_found, rnnpose_stream_t stream);
+
 /* ---- Pose confidence: render-and-compare score of a pose against its frame (no counterpart in the reference) ----
  * rend_depth (B,h,w) fp32 and rend_desc (B,D,h,w) fp32, D = 32: the object's z-buffer and its per-vertex descriptors rendered under
  *   the pose into a WINDOW of the frame, the principal point shifted by the window's integer corner; window (B,2) device int32

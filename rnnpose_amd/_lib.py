@@ -157,6 +157,8 @@ PROTOTYPES = {
     "rnnpose_desc_match_f32": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _i, _i, _f, _i, _f, _i, _p, _z, _p, _p, _p, _p, _p, _p]),
     "rnnpose_pnp_ransac_workspace_bytes": (_z, [_i, _i]),
     "rnnpose_pnp_ransac_f64": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _d, _i, _i, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rnnpose_pnp_ransac_topk_workspace_bytes": (_z, [_i, _i, _i]),
+    "rnnpose_pnp_ransac_topk_f64": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _d, _i, _i, _i, _d, _i, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rnnpose_pose_score_workspace_bytes": (_z, [_i, _i, _i]),
     "rnnpose_pose_score_f64": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p, _p, _p]),
 }

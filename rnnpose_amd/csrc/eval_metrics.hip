@@ -20,6 +20,7 @@
 // points are at the end of this file, so that the host-executed test tier (which builds a fixed list of sources) carries them too.
 #include "desc_match.cuh"
 #include "pnp.cuh"
+#include "pnp_topk.cuh"
 // the pose confidence, placed the same way
 #include "pose_score.cuh"
 
@@ -523,6 +524,43 @@ int rnnpose_pose_score_f64(const float* rend_depth, const float* rend_desc, cons
   hipLaunchKernelGGL(ps::ps_partial_kernel, dim3(B * nchunk), dim3(256), 0, st, rend_depth, rend_desc, window, desc2d, depth_obs, src_index, S, h,
                      w, H, W, nchunk, depth_tol, partial);
   hipLaunchKernelGGL(ps::ps_final_kernel, dim3(B), dim3(64), 0, st, static_cast<const double*>(partial), nchunk, stats, score);
+  return rp::check_launch(fn);
+}
+
+// ---- the K best distinct RANSAC hypotheses, each polished (csrc/pnp_topk.cuh) --------------------------------------------------------------
+size_t rnnpose_pnp_ransac_topk_workspace_bytes(int B, int Hyp, int Kt) { return pnp::topk_workspace_bytes(B, Hyp, Kt); }
+
+int rnnpose_pnp_ransac_topk_f64(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
+                                double tau, int n_polish, int min_count, int Kt, double sep_frac, int min_inliers, void* workspace,
+                                size_t workspace_bytes, float* T, double* cost, int* inliers, int* hyp, unsigned char* inlier_mask,
+                                int* n_inliers, double* final_cost, int* info, int* dup_of, int* n_found, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_pnp_ransac_topk_f64";
+  RP_REQUIRE(X && x && count && K && rnd && workspace && T && cost && inliers && hyp && inlier_mask && n_inliers && final_cost && info && dup_of &&
+                 n_found,
+             fn, "null pointer");
+  RP_REQUIRE(B > 0 && B < 65536 && M > 0 && Hyp > 0 && Hyp <= (1 << 22), fn, "bad size");
+  RP_REQUIRE(Kt >= 1 && Kt <= pnp::kTopkMax, fn, "Kt must lie in [1, 16]");
+  RP_REQUIRE(static_cast<long long>(B) * M * Kt < (1ll << 31), fn, "bad size (too large)");
+  RP_REQUIRE(tau > 0.0 && tau - tau == 0.0, fn, "tau must be positive and finite");
+  RP_REQUIRE(n_polish >= 0 && n_polish <= 64, fn, "n_polish must lie in [0, 64]");
+  RP_REQUIRE(min_count >= 4, fn, "min_count must be >= 4");
+  RP_REQUIRE(sep_frac >= 0.0 && sep_frac - sep_frac == 0.0, fn, "sep_frac must be non-negative and finite");
+  RP_REQUIRE(min_inliers >= 0, fn, "min_inliers must be >= 0");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= pnp::topk_workspace_bytes(B, Hyp, Kt), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  pnp::HypRec* rec = static_cast<pnp::HypRec*>(workspace);
+  double* pol = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + pnp::workspace_bytes(B, Hyp));
+  pnp::TopkBox* box = reinterpret_cast<pnp::TopkBox*>(pol + static_cast<size_t>(B) * Kt * 12);
+  unsigned char* live = static_cast<unsigned char*>(workspace) + pnp::topk_live_offset(B, Hyp, Kt);
+  hipLaunchKernelGGL(pnp::pnp_solve_kernel, dim3(rp::cdiv(Hyp, 64), B), dim3(64), 0, st, X, x, count, M, K, rnd, B, Hyp, min_count, rec);
+  hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
+  hipLaunchKernelGGL(pnp::pnp_topk_select_kernel, dim3(B), dim3(pnp::kSelThreads), 0, st, X, count, M, Hyp, Kt, sep_frac, min_inliers,
+                     static_cast<const pnp::HypRec*>(rec), static_cast<const double*>(cost), static_cast<const int*>(inliers), live, box, hyp, n_found);
+  hipLaunchKernelGGL(pnp::pnp_topk_polish_kernel, dim3(Kt, B), dim3(64), 0, st, X, x, count, M, K, Hyp, Kt, tau, n_polish,
+                     static_cast<const pnp::HypRec*>(rec), static_cast<const int*>(hyp), T, inlier_mask, n_inliers, final_cost, info, pol);
+  hipLaunchKernelGGL(pnp::pnp_topk_dup_kernel, dim3(B), dim3(64), 0, st, Kt, static_cast<const pnp::TopkBox*>(box), static_cast<const double*>(pol),
+                     static_cast<const int*>(info), dup_of);
   return rp::check_launch(fn);
 }
 

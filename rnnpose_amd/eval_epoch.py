@@ -179,8 +179,15 @@ class HipEpoch:
     """PoseRefiner on the HIP mesh rasteriser + device metrics: the refine_fn / metric_fn pair of run_epoch."""
 
     def __init__(self, models, cfg=None, device="cuda", refiner=None, symmetric=("eggbox", "glue"), desc2d=None, occlusion=None,
-                 occlusion_margin=0.0, depth_term=None, init=None, score=False):
-        """score: True or a pose_score.PoseScorer -- `refine` and `refine_frame` also score the poses they return against their frames
+                 occlusion_margin=0.0, depth_term=None, init=None, score=False, init_candidates=1, init_select="score"):
+        """init_candidates = N > 1: an item without a pose gets the N best DISTINCT RANSAC hypotheses of its box
+        (DescriptorPoseInitializer.candidates) instead of the cheapest one.  init_select="score": all n * N of them are scored against
+        the frames in ONE PoseScorer call and every item starts from its highest-scoring valid one (the lowest slot on a tie).
+        init_select="refined" (refine_frame only; `refine` and `initial_poses` select by the score): refine_frame refines ALL N starts
+        of such an item in the same refiner call, scores the refined poses and returns the best valid one per item.  The record
+        `last_init_info` gains candidates (n,N,4,4), candidate_scores (n,N), candidate_valid (n,N) and selected (n).  With
+        init_candidates=1 (the default) nothing new runs.
+        score: True or a pose_score.PoseScorer -- `refine` and `refine_frame` also score the poses they return against their frames
         (the object's descriptors and depth rendered under the pose, compared with the frame's descriptor map and,
         where every item has one, its observed depth) and leave the scores in `last_scores`, the record in `last_score_info`.  False (the
         default): nothing new runs and `last_scores` stays None; `score_poses` / `select_poses` work either way.
@@ -215,8 +222,14 @@ class HipEpoch:
             if init != "descriptors":
                 raise ValueError(f"init must be None, 'descriptors' or a DescriptorPoseInitializer, got {init!r}")
             from .pose_init import DescriptorPoseInitializer
-            init = DescriptorPoseInitializer(models, device=self.device, pixel_center=getattr(self.renderer, "pixel_center", 0.5))
+            init = DescriptorPoseInitializer(models, device=self.device, pixel_center=getattr(self.renderer, "pixel_center", 0.5),
+                                             top_k=init_candidates)
         self.init = init
+        self.init_candidates, self.init_select = int(init_candidates), init_select
+        if init_select not in ("score", "refined"):
+            raise ValueError(f"init_select must be 'score' or 'refined', got {init_select!r}")
+        if self.init_candidates < 1 or (self.init_candidates > 1 and (init is None or getattr(init, "top_k", 1) != self.init_candidates)):
+            raise ValueError(f"init_candidates={init_candidates} needs init='descriptors' or a DescriptorPoseInitializer(top_k={init_candidates})")
         self.last_init_info = None        # initial_poses / refine / refine_frame: the record of the LAST such call (None: it initialised nothing)
         if score is True:
             from .pose_score import PoseScorer
@@ -257,7 +270,7 @@ class HipEpoch:
         else:
             g2 = torch.stack([it.geofea_2d for it in batch]).to(dev)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
-        T0 = self._start_poses(batch, g2, list(range(len(batch))), K)
+        T0 = self._start_poses(batch, g2, list(range(len(batch))), K, firsts=batch)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         out = self.refiner(image, SE3Sequence(matrix=T0[:, None]), K, fea_3d=m.fea_3d.to(dev), Tj_gt=SE3Sequence(matrix=Tg[:, None]),
                            obj_cls=[cls] * len(batch), geofea_3d=m.geofea_3d.to(dev), geofea_2d=g2, **self._observed_depth(batch))
@@ -266,11 +279,12 @@ class HipEpoch:
         self.last_scores = None if self.scorer is None else self.score_poses(batch, poses, scorer=self.scorer)
         return poses
 
-    def _start_poses(self, batch, g2, index, K, skip=(), caller_row=None):
+    def _start_poses(self, batch, g2, index, K, skip=(), caller_row=None, firsts=None):
         """(B,4,4) start poses on the device: every item's pose_init; the items without one (rows in `skip` excepted: they get the
         identity, their start comes from elsewhere) are initialised from the descriptor maps g2 (S,32,H,W) through `index`.
         `last_init_info` becomes the record of this call -- its arrays in ascending order of `rows`, the rows of the CALLER's batch
-        (caller_row[j] = the caller's row of item j, where the batch was regrouped) -- or None when nothing was initialised."""
+        (caller_row[j] = the caller's row of item j, where the batch was regrouped) -- or None when nothing was initialised.
+        firsts: the items the frames of g2 came from (their observed depth goes into the candidates' scores, init_candidates > 1)."""
         dev = self.device
         self.last_init_info = None
         need = [j for j, it in enumerate(batch) if it.pose_init is None and j not in skip]
@@ -282,7 +296,11 @@ class HipEpoch:
         if need:
             boxes = np.stack([np.asarray(batch[j].bbox).astype(np.int32).reshape(4) for j in need])
             rows = torch.as_tensor(need, device=dev)
-            Ti, rec = self.init([batch[j].class_name for j in need], g2, [index[j] for j in need], K[rows].contiguous(), boxes)
+            args = ([batch[j].class_name for j in need], g2, [index[j] for j in need], K[rows].contiguous(), boxes)
+            if self.init_candidates > 1:
+                Ti, rec = self._select_by_score([batch[j] for j in need], *args, firsts)
+            else:
+                Ti, rec = self.init(*args)
             T0[rows] = Ti
             rows = np.asarray(need if caller_row is None else [caller_row[j] for j in need])
             by_row = np.argsort(rows, kind="stable")
@@ -290,6 +308,26 @@ class HipEpoch:
             rec["rows"] = rows[by_row]
             self.last_init_info = rec
         return T0
+
+    def _select_by_score(self, items, names, g2, index, K, boxes, firsts):
+        """The N candidates of every item, all scored in ONE PoseScorer call on the frames' maps (with the observed depth where every
+        frame has one) -> (the highest-scoring VALID candidate of every item, the lowest slot on a tie; the record of `candidates` with
+        its per-slot arrays reduced to the selected slot, plus candidates, candidate_scores, candidate_valid, selected)."""
+        cand, rec = self.init.candidates(names, g2, index, K, boxes)
+        n, N = cand.shape[:2]
+        depth = None if firsts is None or any(it.depth is None for it in firsts) else \
+            torch.stack([it.depth for it in firsts]).to(self.device).float().contiguous()
+        scores = self._score(items, cand.reshape(n * N, 4, 4), N, None, maps=(g2, index, depth)).reshape(n, N).cpu().numpy()
+        sel = self._best_valid(scores, rec["valid"])
+        pick = np.arange(n)
+        out = dict(count=rec["count"], n_inliers=rec["n_inliers"][pick, sel], final_cost=rec["final_cost"][pick, sel], info=rec["info"][pick, sel],
+                   fallback=rec["fallback"], candidates=cand.cpu().numpy(), candidate_scores=scores, candidate_valid=rec["valid"], selected=sel)
+        return cand[torch.arange(n, device=self.device), torch.as_tensor(sel).to(self.device)], out
+
+    @staticmethod
+    def _best_valid(scores, valid):
+        """(n) the first maximum of every row over its valid slots (slot 0 where none is valid: the fallback lives there)."""
+        return np.argmax(np.where(valid, scores, -np.inf), axis=1)
 
     def _frames(self, batch):
         """-> (first item of every distinct frame, the frame index of every item): items with the same non-None frame_id share a frame."""
@@ -320,7 +358,8 @@ class HipEpoch:
         firsts, index = self._frames(batch)
         _, g2 = self._frame_maps(firsts)
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(self.device)
-        return self._start_poses([dataclasses.replace(it, pose_init=None) if it.bbox is not None else it for it in batch], g2, index, K)
+        return self._start_poses([dataclasses.replace(it, pose_init=None) if it.bbox is not None else it for it in batch], g2, index, K,
+                                 firsts=firsts)
 
     def score_poses(self, batch, poses, scorer=None):
         """Render-and-compare confidence of the poses `poses` (B,4,4) of the items of `batch` (any classes, one or several camera
@@ -345,8 +384,9 @@ class HipEpoch:
         index = torch.as_tensor(np.argmax(scores.cpu().numpy(), axis=1)).to(self.device)          # (numpy: the first maximum)
         return cand[torch.arange(B, device=self.device), index], index, scores
 
-    def _score(self, batch, poses, reps, scorer):
-        """Scores of poses (B * reps,4,4): item j owns the rows [j reps, (j + 1) reps)."""
+    def _score(self, batch, poses, reps, scorer, maps=None):
+        """Scores of poses (B * reps,4,4): item j owns the rows [j reps, (j + 1) reps).  maps: (descriptor maps, the frame index of
+        every item, observed depth or None) where the caller holds them already."""
         if scorer is None:
             scorer = self.scorer
         if scorer is None:
@@ -356,9 +396,12 @@ class HipEpoch:
             scorer = self._default_scorer
         if len(batch) < 1 or len(poses) != len(batch) * reps:
             raise ValueError(f"{len(poses)} poses for {len(batch)} items x {reps}")
-        firsts, index = self._frames(batch)
-        _, g2 = self._frame_maps(firsts, want_image=False)
-        depth = None if any(it.depth is None for it in firsts) else torch.stack([it.depth for it in firsts]).to(self.device).float().contiguous()
+        if maps is None:
+            firsts, index = self._frames(batch)
+            _, g2 = self._frame_maps(firsts, want_image=False)
+            depth = None if any(it.depth is None for it in firsts) else torch.stack([it.depth for it in firsts]).to(self.device).float().contiguous()
+        else:
+            g2, index, depth = maps
         rows = [j for j in range(len(batch)) for _ in range(reps)]
         K = np.stack([batch[j].K for j in rows]).astype(np.float32)
         score, self.last_score_info = scorer([batch[j].class_name for j in rows], poses, K, g2.float().contiguous(), [index[j] for j in rows], depth)
@@ -399,6 +442,8 @@ class HipEpoch:
         given nothing new runs."""
         from .transformation import SE3Sequence
         dev = self.device
+        if self.init_candidates > 1 and self.init_select == "refined" and any(it.pose_init is None for it in batch):
+            return self._refine_frame_candidates(batch)
         order = vgroups = None
         given = batch                                                             # (the caller's order: the scores are taken in it)
         if any(it.object_id is not None or it.cam_from_rig is not None for it in batch):
@@ -421,7 +466,7 @@ class HipEpoch:
         K = torch.as_tensor(np.stack([it.K for it in batch]).astype(np.float32)).to(dev)
         # (multi-view: only the FIRST view of a group needs a start, the others are tied to it by the rig)
         tied = () if order is None else {j for j in range(1, len(batch)) if gof[order[j]] == gof[order[j - 1]]}
-        T0 = self._start_poses(batch, g2, index, K, skip=tied, caller_row=order)
+        T0 = self._start_poses(batch, g2, index, K, skip=tied, caller_row=order, firsts=firsts)
         Tg = torch.as_tensor(np.stack([it.pose_gt for it in batch]).astype(np.float32)).to(dev)
         names = [it.class_name for it in batch]
         fea = geo = None                                             # = the renderer's resident tables
@@ -443,6 +488,50 @@ class HipEpoch:
         # (multi-view items are scored view by view, each in its own camera and against its own frame)
         self.last_scores = None if self.scorer is None else self.score_poses(given, poses, scorer=self.scorer)
         return poses
+
+    def _refine_frame_candidates(self, batch):
+        """refine_frame with init_select="refined": every item without a pose becomes its N candidates (same frame, same class, so the
+        frame's maps are still held once), all rows are refined in ONE refiner call and scored in one scorer call, and the best valid
+        refined candidate is returned per item; `last_scores` holds the scores of the returned poses."""
+        if getattr(self.refiner, "occlusion", None) == "frame":
+            raise ValueError("init_select='refined' with occlusion='frame': the candidates of one object would hide each other")
+        if any(it.object_id is not None or it.cam_from_rig is not None for it in batch):
+            raise ValueError("init_select='refined' does not take multi-view groups")
+        need = [j for j, it in enumerate(batch) if it.pose_init is None]
+        bad = [j for j in need if batch[j].bbox is None]
+        if bad:
+            raise ValueError(f"items {bad} have no pose_init: they need a bbox")
+        sub = [batch[j] for j in need]
+        firsts, index = self._frames(sub)
+        _, g2 = self._frame_maps(firsts, want_image=False)
+        K = torch.as_tensor(np.stack([it.K for it in sub]).astype(np.float32)).to(self.device)
+        boxes = np.stack([np.asarray(it.bbox).astype(np.int32).reshape(4) for it in sub])
+        cand, rec = self.init.candidates([it.class_name for it in sub], g2, index, K, boxes)
+        N, ch = cand.shape[1], cand.cpu().numpy()
+        rows, first = [], []                                                      # the expanded batch and every item's first row in it
+        slot = {j: i for i, j in enumerate(need)}
+        for j, it in enumerate(batch):
+            first.append(len(rows))
+            rows += [dataclasses.replace(it, pose_init=ch[slot[j], k].copy()) for k in range(N)] if j in slot else [it]
+        scorer, self.scorer = self.scorer, None                                   # (the rows are scored below, once)
+        try:
+            refined = self.refine_frame(rows)
+        finally:
+            self.scorer = scorer
+        scores = self.score_poses(rows, refined, scorer=scorer)
+        sc = scores.cpu().numpy()
+        cs = np.stack([sc[first[j]:first[j] + N] for j in need])
+        sel = self._best_valid(cs, rec["valid"])
+        take = [first[j] + (int(sel[slot[j]]) if j in slot else 0) for j in range(len(batch))]
+        pick = np.arange(len(need))
+        self.last_init_info = dict(count=rec["count"], n_inliers=rec["n_inliers"][pick, sel], final_cost=rec["final_cost"][pick, sel],
+                                   info=rec["info"][pick, sel], fallback=rec["fallback"], candidates=ch, candidate_scores=cs,
+                                   candidate_valid=rec["valid"], selected=sel, rows=np.asarray(need))
+        take = torch.as_tensor(take, device=self.device)
+        if self.last_depth_stats is not None:
+            self.last_depth_stats = self.last_depth_stats[take]
+        self.last_scores = scores[take]
+        return refined[take]
 
     def bop_metrics(self, batch, pose_pred, want_errors=False):
         """BOP recalls of the poses `pose_pred` (B,4,4) of the items of `batch` (any classes, one or several camera frames):

@@ -2193,6 +2193,80 @@ def pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, T=None):
     return T, cost, inliers, best, mask, n_inl, fcost, info
 
 
+PNP_TOPK_MAX = 16
+_topk_ws = {}
+
+
+def pnp_ransac_topk(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, top_k=4, sep_frac=0.1, min_inliers=0, T=None):
+    """The top_k best DISTINCT hypotheses of the P3P RANSAC, each polished (rnnpose_pnp_ransac_topk_f64).  The
+    inputs of `pnp_ransac`; two poses are distinct when some corner of the correspondences' bounding box moves by more than
+    sep_frac x the box diagonal between them; slot 0 is `pnp_ransac`'s hypothesis, slot k the cheapest one distinct from every slot
+    before it with at least min_inliers inliers.  T (B,top_k,4,4) fp32: written where info == 0 and left as it is elsewhere (None:
+    identities, so an unwritten slot is a harmless pose).
+    -> T (B,top_k,4,4), cost (B,Hyp) fp64, inliers (B,Hyp) int32, hyp (B,top_k) int32 (-1: no such slot), inlier_mask (B,top_k,M)
+       uint8, n_inliers (B,top_k) int32, final_cost (B,top_k) fp64, info (B,top_k) int32, dup_of (B,top_k) int32 (the earlier slot
+       the polish led this one into, or -1), n_found (B) int32.
+    Shapes, dtypes, devices, contiguity and ranges are checked here, on the host (ValueError).  The workspace is cached per
+    (device, B, Hyp, top_k): calls of one shape must not overlap on different streams."""
+    fn = "pnp_ransac_topk"
+    for t, nm in ((X, "X"), (x, "x"), (K, "K")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype.is_floating_point):
+            raise ValueError(f"{fn}: {nm} must be a floating-point GPU tensor")
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
+        raise ValueError(f"{fn}: count must be a contiguous int32 GPU tensor")
+    X, x, K = _chk(X, "X"), _chk(x, "x"), _chk(K, "K")
+    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"{fn}: X must be (B,M,3), got {tuple(X.shape)}")
+    B, M = X.shape[0], X.shape[1]
+    if x.shape != (B, M, 2):
+        raise ValueError(f"{fn}: x must be ({B},{M},2), got {tuple(x.shape)}")
+    if count.shape != (B,):
+        raise ValueError(f"{fn}: count must be ({B},), got {tuple(count.shape)}")
+    if K.shape == (3, 3):
+        K = K.expand(B, 3, 3).contiguous()
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"{fn}: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
+    rnd = random_words(rnd)
+    if not rnd.is_cuda or rnd.dim() != 3 or rnd.shape[0] != B or rnd.shape[2] != 3 or rnd.shape[1] < 1:
+        raise ValueError(f"{fn}: rnd must be a GPU tensor of shape ({B},Hyp,3), got {tuple(rnd.shape)} on {rnd.device}")
+    if not (X.device == x.device == count.device == K.device == rnd.device):
+        raise ValueError(f"{fn}: all tensors must live on one device")
+    Hyp = rnd.shape[1]
+    tau, n_polish, min_count, sep_frac = float(tau), int(n_polish), int(min_count), float(sep_frac)
+    if not (tau > 0.0 and tau < float("inf")) or not 0 <= n_polish <= 64 or min_count < 4:
+        raise ValueError(f"{fn}: tau > 0 and finite, n_polish in [0,64], min_count >= 4; got {tau}, {n_polish}, {min_count}")
+    if int(top_k) != top_k or not 1 <= int(top_k) <= PNP_TOPK_MAX or not 0.0 <= sep_frac < float("inf") or int(min_inliers) != min_inliers or min_inliers < 0:
+        raise ValueError(f"{fn}: top_k in [1,{PNP_TOPK_MAX}], sep_frac >= 0 and finite, min_inliers >= 0; got {top_k}, {sep_frac}, {min_inliers}")
+    Kt, min_inliers = int(top_k), int(min_inliers)
+    dev = X.device
+    if T is None:
+        T = torch.eye(4, device=dev, dtype=F32).repeat(B, Kt, 1, 1)
+    elif not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == F32 and T.is_contiguous() and tuple(T.shape) == (B, Kt, 4, 4) and T.device == dev):
+        raise ValueError(f"{fn}: T must be a contiguous fp32 GPU tensor of shape ({B},{Kt},4,4)")
+    n = int(_lib.load().rnnpose_pnp_ransac_topk_workspace_bytes(B, Hyp, Kt))
+    if n == 0 or B * M * Kt >= 2 ** 31:
+        raise ValueError(f"{fn}: {B} objects x {Hyp} hypotheses x {Kt} slots x {M} correspondences are more than one call takes")
+    key = (dev, B, Hyp, Kt)
+    ws = _topk_ws.get(key)
+    if ws is None:
+        if len(_topk_ws) >= 8:
+            _topk_ws.pop(next(iter(_topk_ws)))
+        ws = _topk_ws[key] = torch.empty(n // 8, device=dev, dtype=torch.int64)
+    cost = torch.empty(B, Hyp, device=dev, dtype=F64)
+    inliers = torch.empty(B, Hyp, device=dev, dtype=torch.int32)
+    hyp = torch.empty(B, Kt, device=dev, dtype=torch.int32)
+    mask = torch.zeros(B, Kt, M, device=dev, dtype=torch.uint8)
+    n_inl = torch.empty(B, Kt, device=dev, dtype=torch.int32)
+    fcost = torch.empty(B, Kt, device=dev, dtype=F64)
+    info = torch.empty(B, Kt, device=dev, dtype=torch.int32)
+    dup_of = torch.empty(B, Kt, device=dev, dtype=torch.int32)
+    n_found = torch.empty(B, device=dev, dtype=torch.int32)
+    _launch("rnnpose_pnp_ransac_topk_f64", _ptr(X), _ptr(x), _ptr(count), M, _ptr(K), _ptr(rnd), B, Hyp, tau, n_polish, min_count, Kt, sep_frac,
+            min_inliers, _ptr(ws), n, _ptr(T), _ptr(cost), _ptr(inliers), _ptr(hyp), _ptr(mask), _ptr(n_inl), _ptr(fcost), _ptr(info),
+            _ptr(dup_of), _ptr(n_found), _stream())
+    return T, cost, inliers, hyp, mask, n_inl, fcost, info, dup_of, n_found
+
+
 # ---- pose confidence: render-and-compare score of a pose against its frame (DESIGN.md section 21; definitions in include/rnnpose_hip.h) ----
 POSE_SCORE_COLUMNS = ("n_rend", "n_out", "n_occ", "n_cons", "n_viol", "n_hole", "n_desc", "sum_cos", "sum_abs_dd", "n_bad")
 _score_ws = {}

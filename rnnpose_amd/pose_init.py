@@ -18,8 +18,10 @@ from . import ops
 class DescriptorPoseInitializer:
     # `tau` and `min_sim` are STARTING VALUES: no measurement of this project supports them ("not claimed").
     def __init__(self, models, device="cuda", step=2, min_sim=0.5, mutual=True, hypotheses=1024, tau=4.0, n_polish=4, seed=0,
-                 pixel_center=0.5, min_count=4):
-        """hypotheses: log 0.01 / log(1 - w^3) of them give 99 % confidence at inlier ratio w; 1024 covers w >= 0.17 (not tuned).
+                 pixel_center=0.5, min_count=4, top_k=1, sep_frac=0.1, min_inliers=0):
+        """top_k, sep_frac, min_inliers: `candidates` returns the top_k best DISTINCT hypotheses (ops.pnp_ransac_topk, DESIGN.md section
+        22; sep_frac is a starting value like tau); `__call__` does not read them.
+        hypotheses: log 0.01 / log(1 - w^3) of them give 99 % confidence at inlier ratio w; 1024 covers w >= 0.17 (not tuned).
         seed: the random words of EVERY call come from a torch.Generator on the device re-seeded with it, so a call is a pure
         function of its inputs."""
         self.models = models
@@ -29,6 +31,9 @@ class DescriptorPoseInitializer:
         self.seed, self.pixel_center = int(seed), float(pixel_center)
         if self.hypotheses < 1:
             raise ValueError("hypotheses must be >= 1")
+        self.top_k, self.sep_frac, self.min_inliers = int(top_k), float(sep_frac), int(min_inliers)
+        if not 1 <= self.top_k <= ops.PNP_TOPK_MAX or not 0.0 <= self.sep_frac < float("inf") or self.min_inliers < 0:
+            raise ValueError(f"top_k in [1,{ops.PNP_TOPK_MAX}], sep_frac >= 0 and finite, min_inliers >= 0")
         self._class = {}        # class -> (descriptors (P,32), points (P,3)) on the device
         self._tables = {}       # tuple of names -> (desc3d, points, offsets on the host, offsets on the device)
         self._gen = None
@@ -85,13 +90,7 @@ class DescriptorPoseInitializer:
         T[:3, 3] = np.linalg.solve(K, np.array([0.5 * (x0 + x1) + self.pixel_center, 0.5 * (y0 + y1) + self.pixel_center, 1.0])) * z
         return T.astype(np.float32)
 
-    def __call__(self, names, geofea_2d, image_index, K, bboxes):
-        """names: B class names; geofea_2d (S,32,H,W) on the device; image_index: B integers (which map every object reads), an
-        ops.SourceIndex or None (object b reads map b); K (3,3) or (B,3,3); bboxes (B,4) [xmin, ymin, xmax, ymax] inclusive pixels
-        (a device int32 tensor as ops.mask_bbox gives, or host values).
-        -> T0 (B,4,4) fp32 on the device and a record of host arrays: count (matches), n_inliers, final_cost, info (0 = RANSAC pose,
-        -1 = none) and fallback (True where the box-centre start was taken instead).  Never raises for a pose it cannot find."""
-        B = len(names)
+    def _inputs(self, B, geofea_2d, K, bboxes):
         if B < 1:
             raise ValueError("no objects")
         geofea_2d = ops._chk(geofea_2d, "geofea_2d")
@@ -102,7 +101,16 @@ class DescriptorPoseInitializer:
         Kt = Kt.contiguous()
         if not isinstance(bboxes, torch.Tensor):
             bboxes = torch.as_tensor(np.asarray(bboxes).astype(np.int32).reshape(B, 4))
-        bboxes = bboxes.to(self.device, torch.int32).contiguous()
+        return geofea_2d, Kt, bboxes.to(self.device, torch.int32).contiguous()
+
+    def __call__(self, names, geofea_2d, image_index, K, bboxes):
+        """names: B class names; geofea_2d (S,32,H,W) on the device; image_index: B integers (which map every object reads), an
+        ops.SourceIndex or None (object b reads map b); K (3,3) or (B,3,3); bboxes (B,4) [xmin, ymin, xmax, ymax] inclusive pixels
+        (a device int32 tensor as ops.mask_bbox gives, or host values).
+        -> T0 (B,4,4) fp32 on the device and a record of host arrays: count (matches), n_inliers, final_cost, info (0 = RANSAC pose,
+        -1 = none) and fallback (True where the box-centre start was taken instead).  Never raises for a pose it cannot find."""
+        B = len(names)
+        geofea_2d, Kt, bboxes = self._inputs(B, geofea_2d, K, bboxes)
         X, x, _, _, count = self.match(names, geofea_2d, image_index, bboxes)
         T, _, _, _, _, n_inl, fcost, info = ops.pnp_ransac(X, x, count, Kt, self.random_words(B), self.tau, self.n_polish, self.min_count)
         rec = dict(count=count.cpu().numpy(), n_inliers=n_inl.cpu().numpy(), final_cost=fcost.cpu().numpy(), info=info.cpu().numpy())
@@ -112,4 +120,29 @@ class DescriptorPoseInitializer:
             rows = np.nonzero(rec["fallback"])[0]
             fb = np.stack([self.fallback(names[j], Kh[j], bh[j], geofea_2d.shape[-2:]) for j in rows])
             T[torch.as_tensor(rows, device=self.device)] = torch.as_tensor(fb).to(self.device)
+        return T, rec
+
+    def candidates(self, names, geofea_2d, image_index, K, bboxes):
+        """The arguments of `__call__`.  -> T (B,top_k,4,4) fp32 on the device and a record of host arrays: count (B), hyp, n_inliers,
+        final_cost, info, dup_of (B,top_k each), n_found (B), valid (B,top_k) = (info == 0) & (dup_of < 0) and fallback (B): True where
+        NO slot is valid -- slot 0 then holds the box-centre start of `__call__`.  Every slot that is not valid holds a copy of slot 0's
+        pose (of the first valid slot's, should slot 0's own polish have failed), so whatever renders it renders something sane.  Never raises for a pose it cannot find."""
+        B = len(names)
+        geofea_2d, Kt, bboxes = self._inputs(B, geofea_2d, K, bboxes)
+        X, x, _, _, count = self.match(names, geofea_2d, image_index, bboxes)
+        T, _, _, hyp, _, n_inl, fcost, info, dup_of, n_found = ops.pnp_ransac_topk(
+            X, x, count, Kt, self.random_words(B), self.tau, self.n_polish, self.min_count, self.top_k, self.sep_frac, self.min_inliers)
+        rec = dict(count=count.cpu().numpy(), hyp=hyp.cpu().numpy(), n_inliers=n_inl.cpu().numpy(), final_cost=fcost.cpu().numpy(),
+                   info=info.cpu().numpy(), dup_of=dup_of.cpu().numpy(), n_found=n_found.cpu().numpy())
+        rec["valid"] = (rec["info"] == 0) & (rec["dup_of"] < 0)
+        rec["fallback"] = ~rec["valid"].any(1)
+        if rec["fallback"].any():
+            Kh, bh = Kt.cpu().numpy(), bboxes.cpu().numpy()
+            rows = np.nonzero(rec["fallback"])[0]
+            fb = np.stack([self.fallback(names[j], Kh[j], bh[j], geofea_2d.shape[-2:]) for j in rows])
+            T[torch.as_tensor(rows, device=self.device), 0] = torch.as_tensor(fb).to(self.device)
+        # (the copy comes from the FIRST valid slot: slot 0, unless its own polish failed where a later slot's did not)
+        first = torch.as_tensor(rec["valid"].argmax(1)).to(self.device)
+        src = T[torch.arange(B, device=self.device), first][:, None]
+        T = torch.where(torch.as_tensor(rec["valid"]).to(self.device)[:, :, None, None], T, src).contiguous()
         return T, rec

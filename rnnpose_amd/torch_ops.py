@@ -37,6 +37,7 @@ _SCHEMAS = {
     "lm_step_views": "(Tensor target, Tensor weight, Tensor depth, Tensor K, Tensor G, Tensor group_start, Tensor cam_from_rig, int num_iters=1, float ep_lambda=100.0, float lm_lambda=1e-4, float max_update=1.0) -> (Tensor G_new, Tensor xi, Tensor Hg, Tensor bg)",
     "desc_match": "(Tensor desc3d, Tensor points, Tensor pt_off, Tensor desc2d, Tensor src_index, Tensor bbox, int step=2, float min_sim=0.5, bool mutual=True, float pixel_center=0.5, int M=0) -> (Tensor X, Tensor x, Tensor sim, Tensor point_idx, Tensor count)",
     "pnp_ransac": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4) -> (Tensor T, Tensor cost, Tensor inliers, Tensor best, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info)",
+    "pnp_ransac_topk": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4, int top_k=4, float sep_frac=0.1, int min_inliers=0) -> (Tensor T, Tensor cost, Tensor inliers, Tensor hyp, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info, Tensor dup_of, Tensor n_found)",
     "pose_score": "(Tensor rend_depth, Tensor rend_desc, Tensor window, Tensor desc2d, Tensor src_index, Tensor? depth_obs=None, float depth_tol=0.015) -> (Tensor stats, Tensor score)",
 }
 
@@ -140,6 +141,10 @@ def _pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4):
     return ops.pnp_ransac(X, x, count.to(torch.int32).contiguous(), K, rnd, tau, n_polish, min_count)
 
 
+def _pnp_ransac_topk(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, top_k=4, sep_frac=0.1, min_inliers=0):
+    return ops.pnp_ransac_topk(X, x, count.to(torch.int32).contiguous(), K, rnd, tau, n_polish, min_count, top_k, sep_frac, min_inliers)
+
+
 def _pose_score(rend_depth, rend_desc, window, desc2d, src_index, depth_obs=None, depth_tol=0.015):
     """src_index (B,): an integer tensor, checked on the host (ValueError) before anything is launched; window (B,2) any integer dtype."""
     return ops.pose_score(rend_depth, rend_desc, window.to(torch.int32).contiguous(), desc2d, src_index, depth_obs, depth_tol)
@@ -162,6 +167,14 @@ def _f_pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4):
     e = lambda shape, dt: X.new_empty(shape, dtype=dt)
     return (e((B, 4, 4), torch.float32), e((B, Hyp), torch.float64), e((B, Hyp), torch.int32), e((B,), torch.int32), e((B, M), torch.uint8),
             e((B,), torch.int32), e((B,), torch.float64), e((B,), torch.int32))
+
+
+def _f_pnp_ransac_topk(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, top_k=4, sep_frac=0.1, min_inliers=0):
+    B, M, Hyp, Kt = X.shape[0], X.shape[1], rnd.shape[1], top_k
+    e = lambda shape, dt: X.new_empty(shape, dtype=dt)
+    return (e((B, Kt, 4, 4), torch.float32), e((B, Hyp), torch.float64), e((B, Hyp), torch.int32), e((B, Kt), torch.int32),
+            e((B, Kt, M), torch.uint8), e((B, Kt), torch.int32), e((B, Kt), torch.float64), e((B, Kt), torch.int32), e((B, Kt), torch.int32),
+            e((B,), torch.int32))
 
 
 def _f_corr_pyramid(fmap1, fmap2, levels=4):
@@ -247,7 +260,7 @@ def register():
              "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
              "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd),
              "desc_match": (_desc_match, _f_desc_match), "pnp_ransac": (_pnp_ransac, _f_pnp_ransac),
-             "pose_score": (_pose_score, _f_pose_score)}
+             "pose_score": (_pose_score, _f_pose_score), "pnp_ransac_topk": (_pnp_ransac_topk, _f_pnp_ransac_topk)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]

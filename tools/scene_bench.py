@@ -47,7 +47,15 @@ against a threshold.
 times the pose confidence on the frame and its observed depth, at the ground-truth poses: the kernel pair alone
 (ops.pose_score on tensors rendered beforehand, with and without the depth), `PoseScorer` as a whole (window, render, kernel pair, record),
 `HipEpoch.score_poses`, and `refine_frame` with `score=True` next to the plain one, alternating inside every run.  The scores at the
-ground-truth poses, at the initial poses and of the refined poses are recorded.  Nothing is compared against a threshold."""
+ground-truth poses, at the initial poses and of the refined poses are recorded.  Nothing is compared against a threshold.
+
+    python tools/scene_bench.py --topk [--out profiles/scene_bench_topk.json]
+
+times the top-K distinct RANSAC hypotheses on the frame, boxes and matches as for --init: ops.pnp_ransac against
+ops.pnp_ransac_topk at 1, 4, 8 and 16 slots on the same matches and random words; `initial_poses` with init_candidates 1 and 4; and
+`refine_frame` on items without a pose with init_candidates 1, with 4 selected by the score and with 4 selected after refinement -- all
+alternating inside every run.  How many objects changed their start through the score is recorded.  Nothing is compared against a
+threshold."""
 from __future__ import annotations
 
 import argparse
@@ -361,6 +369,76 @@ def init_bench(a, models, cfg, net, hip, items, given, size, cover):
             json.dump(res, fh, indent=1)
 
 
+def topk_bench(a, models, cfg, net, hip, items, given, size, cover):
+    """--topk: the K best distinct RANSAC hypotheses, and the selection among them by the pose score"""
+    import dataclasses
+    H, W = size
+    n = len(items)
+    depth_dev = items[0].depth.cuda()
+
+    def epoch(**kw):
+        e = ee.HipEpoch(models, cfg=cfg, desc2d=net, init="descriptors", **kw)
+        e.refiner.load_state_dict(hip.refiner.state_dict())
+        return e
+    hip_1, hip_4, hip_r = epoch(), epoch(init_candidates=4), epoch(init_candidates=4, init_select="refined")
+    ini = hip_4.init
+    names = [it.class_name for it in items]
+    Tg = torch.as_tensor(np.stack([it.pose_gt for it in items]).astype(np.float32)).cuda()
+    K = torch.as_tensor(np.stack([it.K for it in items]).astype(np.float32)).cuda()
+    boxes = ops.mask_bbox(hip_1.renderer.render_zbuf(names, Tg, K, (H, W)).float().contiguous()).cpu().numpy() + np.array([-8, -8, 8, 8], np.int32)
+    boxes_dev = torch.as_tensor(boxes).cuda()
+    bare = [ee.EvalItem(it.class_name, it.image, it.K, None, it.pose_gt, it.geofea_2d, frame_id=it.frame_id, depth=depth_dev, bbox=bb)
+            for it, bb in zip(given, boxes)]
+    g2 = given[0].geofea_2d[None].float().contiguous()
+    idx = ops.SourceIndex([0] * n, 1, "cuda")
+    X, x, sim, pidx, count = ini.match(names, g2, idx, boxes_dev)
+    words = ops.random_words(ini.random_words(n))
+    topk = lambda k: ops.pnp_ransac_topk(X, x, count, K, words, ini.tau, ini.n_polish, ini.min_count, k, ini.sep_frac, ini.min_inliers)
+    T1 = hip_1.initial_poses(bare)
+    T4 = hip_4.initial_poses(bare)
+    rec = hip_4.last_init_info
+    hip_r.refine_frame(bare)
+    rec_r = hip_r.last_init_info
+    found = {k: [int(v) for v in topk(k)[9].cpu()] for k in (4, 8, 16)}
+    fns = {"ransac_and_polish": lambda: ops.pnp_ransac(X, x, count, K, words, ini.tau, ini.n_polish, ini.min_count)}
+    for k in (1, 4, 8, 16):
+        fns[f"topk_{k}"] = (lambda k: lambda: topk(k))(k)
+    fns.update({"initial_poses_1": lambda: hip_1.initial_poses(bare), "initial_poses_4": lambda: hip_4.initial_poses(bare),
+                "refine_frame_1": lambda: hip_1.refine_frame(bare), "refine_frame_4_score": lambda: hip_4.refine_frame(bare),
+                "refine_frame_4_refined": lambda: hip_r.refine_frame(bare)})
+    times = time_alternately(fns, a.runs, a.warmup)
+
+    def add(T):
+        out = []
+        for j, it in enumerate(items):
+            v = models[it.class_name].verts.astype(np.float64)
+            t, g = T[j].cpu().numpy().astype(np.float64), np.asarray(it.pose_gt, np.float64)
+            out.append(float(np.linalg.norm((v @ t[:3, :3].T + t[:3, 3]) - (v @ g[:3, :3].T + g[:3, 3]), axis=1).mean() / models[it.class_name].diameter))
+        return out
+    med = lambda k: times[k]["median_ms"]
+    res = dict(device=torch.cuda.get_device_name(0), objects=n, size=[H, W], crop=list(cfg.zoom_crop_size), schedule=[cfg.RENDER_ITER_COUNT, cfg.ITER_COUNT],
+               verts_per_object=int(next(iter(models.values())).verts.shape[0]), frame_coverage=cover, runs=a.runs, warmup=a.warmup,
+               hypotheses=ini.hypotheses, tau=ini.tau, n_polish=ini.n_polish, sep_frac=ini.sep_frac, min_inliers=ini.min_inliers,
+               matches=[int(c) for c in rec["count"]], n_found=found, candidate_valid=rec["candidate_valid"].astype(int).tolist(),
+               candidate_scores=[[float(v) for v in r] for r in rec["candidate_scores"]], selected_by_score=[int(v) for v in rec["selected"]],
+               starts_changed_by_score=int((rec["selected"] != 0).sum()), selected_after_refinement=[int(v) for v in rec_r["selected"]],
+               results_changed_by_refined_selection=int((rec_r["selected"] != 0).sum()),
+               add_over_diameter_candidates_1=add(T1), add_over_diameter_candidates_4=add(T4), device_ms=times,
+               note="ransac_and_polish = ops.pnp_ransac, topk_K = ops.pnp_ransac_topk with K slots, on the same matches and random words drawn "
+                    "beforehand; initial_poses_1 / _4 = HipEpoch.initial_poses with init_candidates 1 / 4 (4: candidates + ONE PoseScorer call "
+                    "over 4 n poses with the observed depth + the choice on the host); refine_frame_* on items without a pose.  The frame's "
+                    "descriptor map is RENDERED from the models' own hash-noise vertex descriptors and the refiner's weights are random numbers: "
+                    "the matches have one mode, so this shows the mechanism and its cost and says NOTHING about a trained network; nothing is "
+                    "compared against a threshold")
+    print("RANSAC + polish %.3f ms   top-K: " % med("ransac_and_polish") + "  ".join(f"K={k} {med(f'topk_{k}'):.3f} ms" for k in (1, 4, 8, 16)))
+    print(f"initial_poses: 1 candidate {med('initial_poses_1'):.3f} ms   4 candidates {med('initial_poses_4'):.3f} ms")
+    print(f"refine_frame: 1 candidate {med('refine_frame_1'):.2f} ms   4 by score {med('refine_frame_4_score'):.2f} ms   4 refined {med('refine_frame_4_refined'):.2f} ms")
+    print(f"  n_found {found}  selected by score {res['selected_by_score']} ({res['starts_changed_by_score']} of {n} starts changed)  after refinement {res['selected_after_refinement']}")
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def score_bench(a, models, cfg, net, hip, items, given, size, cover):
     """--score: the pose confidence on the frame, with its observed depth"""
     n = len(items)
@@ -426,6 +504,7 @@ def main():
     ap.add_argument("--views", action="store_true", help="measure multi-view refinement instead: 4 objects x 2 cameras, grouped against ungrouped")
     ap.add_argument("--init", action="store_true", help="time the pose initialiser (descriptor matcher + P3P RANSAC) on the frame instead (see above)")
     ap.add_argument("--score", action="store_true", help="time the pose confidence (render-and-compare score) on the frame instead (see above)")
+    ap.add_argument("--topk", action="store_true", help="time the top-K distinct RANSAC hypotheses and the selection by the pose score instead (see above)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_bench measures on the GPU; none is visible")
@@ -453,6 +532,8 @@ def main():
         return init_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
     if a.score:
         return score_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
+    if a.topk:
+        return topk_bench(a, models, cfg, net, hip, items, given, (H, W), cover)
 
     per_object = lambda its: [hip.refine(it.class_name, [it]) for it in its]
     whole = time_alternately({"a_per_object": lambda: per_object(bare), "b_frame": lambda: hip.refine_frame(bare)}, a.runs, a.warmup)
