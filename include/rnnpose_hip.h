@@ -427,7 +427,11 @@ int rnnpose_f16x3_saturation_peek(unsigned long long* d_count, rnnpose_stream_t 
  * statistics hold for every size -- rnnpose_stem_tiles reports h_exact = 1 always since r03; the field is kept for callers).
  * r06: the kernel is PERSISTENT -- two workgroups per CU walk the tile list with the packed weights resident in LDS and the patch split
  * into fp16 hi / lo once per tile; rnnpose_stem_workgroups(n) caps the number of workgroups (tests: many tiles per workgroup at small
- * sizes; 0 = default).  Results do not depend on it. */
+ * sizes; 0 = default).  Results do not depend on it.
+ * LIMITS: out, bias and the packed weights 16-byte aligned; N * tiles < 2^31; and, because the kernel addresses image and output with
+ * 32-bit byte offsets, the image (N*3*H*W*4 bytes) and the output (N*ceil(H/2)*ceil(W/2)*256 bytes), each extended by the overhang of
+ * the last 8 x 16 output tile (its 21 x 37 input patch), must stay below 2^31 bytes: 109 frames of 480 x 640 are accepted, 110 are
+ * refused ("batch too large for 32-bit byte offsets") before anything is launched -- callers split larger batches. */
 long long rnnpose_stem_packed_halfs(void);
 int rnnpose_stem_workgroups(int max_workgroups);
 int rnnpose_stem_pack_weights_f16x3(const float* w_oihw, float w_scale, void* w_hi, void* w_lo, rnnpose_stream_t stream);

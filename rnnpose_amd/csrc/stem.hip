@@ -512,6 +512,17 @@ int rnnpose_stem_conv7x7_s2_f16x3(const float* img_nchw, int N, int H, int W, in
   // (tile_stats: ragged tilings included -- pixels outside the image are dropped before they enter the sums)
   const long long blocks = static_cast<long long>(N) * tiles_x * tiles_y;
   RP_REQUIRE(blocks < (1LL << 31), fn, "too many tiles");
+  {
+    // The kernel addresses image and output with 32-bit byte offsets (stem_conv7x7_s2_kernel: `base + e_rel[j]`, `obase + off`).  Both
+    // are formed for every element of a tile, also for those a ragged tile leaves outside the image (they are not accessed, but their
+    // offsets are computed): the largest of each -- last image, last tile, last patch row / output row of the tile -- must stay below 2^31.
+    const long long in_end = ((((N - 1LL) * 3 * H + 2LL * (tiles_y - 1) * TH - 3) * W + 2LL * (tiles_x - 1) * TW - 3) +
+                              ((2LL * H + PH - 1) * W + PW - 1)) * 4 + 4;
+    const long long out_end = ((((N - 1LL) * Ho + tiles_y * TH - 1LL) * Wo + tiles_x * TW - 1LL) * CO + CO) * 4;
+    RP_REQUIRE(in_end <= (1LL << 31) && out_end <= (1LL << 31), fn,
+               "batch too large for 32-bit byte offsets: N*3*H*W*4 (image) and N*ceil(H/2)*ceil(W/2)*256 (output) bytes, tile "
+               "overhang included, must stay below 2^31");
+  }
 #if STEM_V2
   // persistent: two workgroups per CU (or fewer: one per tile of the XCD chunks), a multiple of 8
   const int ntiles = static_cast<int>(blocks);

@@ -223,7 +223,8 @@ FILES = ["tests/test_gpu_parity.py", "tests/test_gpu_conv.py", "tests/test_gpu_e
          "tests/test_gpu_zoom_edges.py",                                         # (no large shapes: the whole module runs here)
          "tests/test_gpu_glue_edges.py", "tests/test_gpu_corr_edges.py",
          "tests/test_gpu_point_edges.py",                                        # (no large shapes either: 16384 x 40 x 70 takes the emulation under a second)
-         "tests/test_gpu_range_guard.py"]                                        # (at most 3 x 11 x 19 pixels per launch, one stride-2 layer of 20 x 32: the whole module)
+         "tests/test_gpu_range_guard.py",                                        # (at most 3 x 11 x 19 pixels per launch, one stride-2 layer of 20 x 32: the whole module)
+         "tests/test_gpu_stem_mask_edges.py"]                                    # (at most 20 x 16 x 32 image pixels / 75 low-resolution pixels per launch: the whole module)
 
 # The strip convolution kernels (LDS-DMA by inline assembly on the GPU; tests/host_exec/build_host.py gives their scratch copy host
 # versions of the request / wait helpers): both strip heights, split-tensor (DMA) and fp32 (register-path) sources, 3x3 / 1x5 / 5x1,
@@ -285,8 +286,8 @@ def test_gpu_parity_tests_pass_on_the_host_executed_kernels(host_lib):
     _passed(b, len(STRIP_IDS))
     # 88: the small-shape cases of tests/test_gpu_lm_geometry.py, 70: those of tests/test_gpu_raster_edges.py, 94: all of tests/test_gpu_zoom_edges.py,
     # 90: those of tests/test_gpu_glue_edges.py, 52: those of tests/test_gpu_corr_edges.py (all but the four entries of its 48 x 56 volume),
-    # 73: all of tests/test_gpu_point_edges.py, 93: all of tests/test_gpu_range_guard.py
-    _passed(a, 95 + 88 + 70 + 94 + 90 + 52 + 73 + 93)
+    # 73: all of tests/test_gpu_point_edges.py, 93: all of tests/test_gpu_range_guard.py, 145: all of tests/test_gpu_stem_mask_edges.py
+    _passed(a, 95 + 88 + 70 + 94 + 90 + 52 + 73 + 93 + 145)
 
 
 def test_harness_model(tmp_path):
