@@ -479,6 +479,27 @@ int rnnpose_desc_match_f32(const float* desc3d, const float* points, const int* 
   return rp::check_launch(fn);
 }
 
+// The argument checks both RANSAC entry points make, in their order; Kt = 1 for the single pose.  -> 0, or 1 with the error set for `fn`.
+static int pnp_check_args(const char* fn, bool pointers, int B, int M, int Hyp, int Kt, double tau, int n_polish, int min_count) {
+  RP_REQUIRE(pointers, fn, "null pointer");
+  RP_REQUIRE(B > 0 && B < 65536 && M > 0 && Hyp > 0 && Hyp <= (1 << 22), fn, "bad size");
+  RP_REQUIRE(Kt >= 1 && Kt <= pnp::kTopkMax, fn, "Kt must lie in [1, 16]");
+  RP_REQUIRE(static_cast<long long>(B) * M * Kt < (1ll << 31), fn, "bad size (too large)");
+  RP_REQUIRE(tau > 0.0 && tau - tau == 0.0, fn, "tau must be positive and finite");
+  RP_REQUIRE(n_polish >= 0 && n_polish <= 64, fn, "n_polish must lie in [0, 64]");
+  RP_REQUIRE(min_count >= 4, fn, "min_count must be >= 4");
+  return 0;
+}
+
+// The minimal solves and their scores: the head of the workspace holds every hypothesis's candidates afterwards.
+static pnp::HypRec* pnp_solve_and_score(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
+                                        double tau, int min_count, void* workspace, double* cost, int* inliers, hipStream_t st) {
+  pnp::HypRec* rec = static_cast<pnp::HypRec*>(workspace);
+  hipLaunchKernelGGL(pnp::pnp_solve_kernel, dim3(rp::cdiv(Hyp, 64), B), dim3(64), 0, st, X, x, count, M, K, rnd, B, Hyp, min_count, rec);
+  hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
+  return rec;
+}
+
 size_t rnnpose_pnp_ransac_workspace_bytes(int B, int Hyp) { return pnp::workspace_bytes(B, Hyp); }
 
 int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int M, const float* K, const unsigned* rnd, int B, int Hyp,
@@ -486,19 +507,13 @@ int rnnpose_pnp_ransac_f64(const float* X, const float* x, const int* count, int
                            int* inliers, int* best, unsigned char* inlier_mask, int* n_inliers, double* final_cost, int* info,
                            rnnpose_stream_t stream) {
   const char* fn = "rnnpose_pnp_ransac_f64";
-  RP_REQUIRE(X && x && count && K && rnd && workspace && T && cost && inliers && best && inlier_mask && n_inliers && final_cost && info, fn,
-             "null pointer");
-  RP_REQUIRE(B > 0 && B < 65536 && M > 0 && Hyp > 0 && Hyp <= (1 << 22), fn, "bad size");
-  RP_REQUIRE(static_cast<long long>(B) * M < (1ll << 31), fn, "bad size (too large)");
-  RP_REQUIRE(tau > 0.0 && tau - tau == 0.0, fn, "tau must be positive and finite");
-  RP_REQUIRE(n_polish >= 0 && n_polish <= 64, fn, "n_polish must lie in [0, 64]");
-  RP_REQUIRE(min_count >= 4, fn, "min_count must be >= 4");
+  if (pnp_check_args(fn, X && x && count && K && rnd && workspace && T && cost && inliers && best && inlier_mask && n_inliers && final_cost && info,
+                     B, M, Hyp, 1, tau, n_polish, min_count))
+    return 1;
   RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
   RP_REQUIRE(workspace_bytes >= pnp::workspace_bytes(B, Hyp), fn, "workspace too small");
   hipStream_t st = rp::as_stream(stream);
-  pnp::HypRec* rec = static_cast<pnp::HypRec*>(workspace);
-  hipLaunchKernelGGL(pnp::pnp_solve_kernel, dim3(rp::cdiv(Hyp, 64), B), dim3(64), 0, st, X, x, count, M, K, rnd, B, Hyp, min_count, rec);
-  hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
+  pnp::HypRec* rec = pnp_solve_and_score(X, x, count, M, K, rnd, B, Hyp, tau, min_count, workspace, cost, inliers, st);
   hipLaunchKernelGGL(pnp::pnp_polish_kernel, dim3(B), dim3(64), 0, st, X, x, count, M, K, B, Hyp, tau, n_polish, rec, cost, T, best, inlier_mask,
                      n_inliers, final_cost, info);
   return rp::check_launch(fn);
@@ -535,26 +550,19 @@ int rnnpose_pnp_ransac_topk_f64(const float* X, const float* x, const int* count
                                 size_t workspace_bytes, float* T, double* cost, int* inliers, int* hyp, unsigned char* inlier_mask,
                                 int* n_inliers, double* final_cost, int* info, int* dup_of, int* n_found, rnnpose_stream_t stream) {
   const char* fn = "rnnpose_pnp_ransac_topk_f64";
-  RP_REQUIRE(X && x && count && K && rnd && workspace && T && cost && inliers && hyp && inlier_mask && n_inliers && final_cost && info && dup_of &&
-                 n_found,
-             fn, "null pointer");
-  RP_REQUIRE(B > 0 && B < 65536 && M > 0 && Hyp > 0 && Hyp <= (1 << 22), fn, "bad size");
-  RP_REQUIRE(Kt >= 1 && Kt <= pnp::kTopkMax, fn, "Kt must lie in [1, 16]");
-  RP_REQUIRE(static_cast<long long>(B) * M * Kt < (1ll << 31), fn, "bad size (too large)");
-  RP_REQUIRE(tau > 0.0 && tau - tau == 0.0, fn, "tau must be positive and finite");
-  RP_REQUIRE(n_polish >= 0 && n_polish <= 64, fn, "n_polish must lie in [0, 64]");
-  RP_REQUIRE(min_count >= 4, fn, "min_count must be >= 4");
+  if (pnp_check_args(fn, X && x && count && K && rnd && workspace && T && cost && inliers && hyp && inlier_mask && n_inliers && final_cost && info &&
+                             dup_of && n_found,
+                     B, M, Hyp, Kt, tau, n_polish, min_count))
+    return 1;
   RP_REQUIRE(sep_frac >= 0.0 && sep_frac - sep_frac == 0.0, fn, "sep_frac must be non-negative and finite");
   RP_REQUIRE(min_inliers >= 0, fn, "min_inliers must be >= 0");
   RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
   RP_REQUIRE(workspace_bytes >= pnp::topk_workspace_bytes(B, Hyp, Kt), fn, "workspace too small");
   hipStream_t st = rp::as_stream(stream);
-  pnp::HypRec* rec = static_cast<pnp::HypRec*>(workspace);
+  pnp::HypRec* rec = pnp_solve_and_score(X, x, count, M, K, rnd, B, Hyp, tau, min_count, workspace, cost, inliers, st);
   double* pol = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + pnp::workspace_bytes(B, Hyp));
   pnp::TopkBox* box = reinterpret_cast<pnp::TopkBox*>(pol + static_cast<size_t>(B) * Kt * 12);
   unsigned char* live = static_cast<unsigned char*>(workspace) + pnp::topk_live_offset(B, Hyp, Kt);
-  hipLaunchKernelGGL(pnp::pnp_solve_kernel, dim3(rp::cdiv(Hyp, 64), B), dim3(64), 0, st, X, x, count, M, K, rnd, B, Hyp, min_count, rec);
-  hipLaunchKernelGGL(pnp::pnp_score_kernel, dim3(rp::cdiv(Hyp, 4), B), dim3(256), 0, st, X, x, count, M, K, B, Hyp, tau, rec, cost, inliers);
   hipLaunchKernelGGL(pnp::pnp_topk_select_kernel, dim3(B), dim3(pnp::kSelThreads), 0, st, X, count, M, Hyp, Kt, sep_frac, min_inliers,
                      static_cast<const pnp::HypRec*>(rec), static_cast<const double*>(cost), static_cast<const int*>(inliers), live, box, hyp, n_found);
   hipLaunchKernelGGL(pnp::pnp_topk_polish_kernel, dim3(Kt, B), dim3(64), 0, st, X, x, count, M, K, Hyp, Kt, tau, n_polish,

@@ -2,6 +2,7 @@
 //   pnp_solve_kernel   one thread per (object, hypothesis): the minimal solve (csrc/pnp_math.cuh), up to four candidates into the workspace
 //   pnp_score_kernel   one wave per (object, hypothesis): every candidate against all correspondences; the cheapest one is the hypothesis
 //   pnp_polish_kernel  one wave per object: the cheapest hypothesis (lowest h on a tie), n_polish Gauss-Newton steps, final inlier set
+// The polish is polish_body, which pnp_topk_polish_kernel (csrc/pnp_topk.cuh) runs on its slots too.
 // Sums go over the lanes' strided partial sums and then through a fixed xor butterfly, counts are integers: two launches are bit-identical.
 // Included by csrc/eval_metrics.hip (the entry points are there, next to the evaluator's other per-object fp64 kernels).
 #pragma once
@@ -110,42 +111,40 @@ __global__ __launch_bounds__(256) void pnp_score_kernel(const float* __restrict_
   }
 }
 
-__global__ __launch_bounds__(64) void pnp_polish_kernel(const float* __restrict__ X, const float* __restrict__ x, const int* __restrict__ count,
-                                                       int M, const float* __restrict__ K, int B, int Hyp, double tau, int n_polish,
-                                                       const HypRec* __restrict__ rec, const double* __restrict__ cost, float* __restrict__ T,
-                                                       int* __restrict__ best, unsigned char* __restrict__ inlier_mask,
-                                                       int* __restrict__ n_inliers, double* __restrict__ final_cost, int* __restrict__ info) {
-  const int b = blockIdx.x, lane = threadIdx.x;
+// the better of two (cost, hypothesis) keys: the lower cost, the lower h on a tie; h < 0 is no key
+__device__ __forceinline__ void better_key(double& bc, int& bh, double oc, int oh) {
+  if (oh >= 0 && (bh < 0 || oc < bc || (oc == bc && oh < bh))) {
+    bc = oc;
+    bh = oh;
+  }
+}
+
+// the cheapest candidate of hypothesis h of object b -> Rt; false, and Rt as it was, when h is no hypothesis or has no candidate
+__device__ __forceinline__ bool load_candidate(const HypRec* __restrict__ rec, int b, int Hyp, int h, double Rt[12]) {
+  if (h < 0 || h >= Hyp) return false;
+  const HypRec* hr = rec + static_cast<size_t>(b) * Hyp + h;
+  const int c = hr->best;
+  if (c < 0 || c >= 4) return false;
+  for (int e = 0; e < 12; ++e) Rt[e] = hr->Rt[c][e];
+  return true;
+}
+
+// One wave polishes hypothesis h of object b (h < 0: none) and writes the outputs of `row` (the object, or its slot): n_polish
+// Gauss-Newton steps on the inliers of the current pose, the finite test, the final inlier set and MSAC cost.  T is written only
+// where info is 0.  kPol: the polished pose also goes to pol[row] in fp64 (the top-K path's dup_of reads it).
+template <bool kPol>
+__device__ __forceinline__ void polish_body(const float* __restrict__ X, const float* __restrict__ x, const int* __restrict__ count, int M,
+                                            const float* __restrict__ K, int b, double tau, int n_polish, const HypRec* __restrict__ rec,
+                                            int Hyp, int h, size_t row, float* __restrict__ T, unsigned char* __restrict__ inlier_mask,
+                                            int* __restrict__ n_inliers, double* __restrict__ final_cost, int* __restrict__ info,
+                                            double* __restrict__ pol) {
+  const int lane = threadIdx.x;
   const int cnt = clamp_count(count, b, M);
   const pnpm::Cam cam = load_cam(K, b);
   const double tau2 = tau * tau;
-  // the cheapest hypothesis, the lowest h on a tie
-  double bc = inf_d();
-  int bh = -1;
-  for (int h = lane; h < Hyp; h += 64) {
-    const double c = cost[static_cast<size_t>(b) * Hyp + h];
-    if (c < bc) {
-      bc = c;
-      bh = h;
-    }
-  }
-  for (int o = 32; o >= 1; o >>= 1) {
-    const double oc = rp::shfl_xor_f64(bc, o);
-    const int oh = __shfl_xor(bh, o);
-    if (oh >= 0 && (bh < 0 || oc < bc || (oc == bc && oh < bh))) {
-      bc = oc;
-      bh = oh;
-    }
-  }
-  bool ok = bh >= 0;
   double Rt[12];
   for (int e = 0; e < 12; ++e) Rt[e] = 0.0;
-  if (ok) {
-    const HypRec* hr = rec + static_cast<size_t>(b) * Hyp + bh;
-    ok = hr->best >= 0 && hr->best < 4;
-    if (ok)
-      for (int e = 0; e < 12; ++e) Rt[e] = hr->Rt[hr->best][e];
-  }
+  bool ok = load_candidate(rec, b, Hyp, h, Rt);
   for (int it = 0; it < n_polish && ok; ++it) {          // (ok is the same in every lane: the control flow stays wave-uniform)
     double H[21], g[6];
     for (int e = 0; e < 21; ++e) H[e] = 0.0;
@@ -172,7 +171,7 @@ __global__ __launch_bounds__(64) void pnp_polish_kernel(const float* __restrict_
       load_corr(X, x, static_cast<size_t>(b) * M + i, P, p);
       in = pnpm::score_point(Rt, cam, P, p, tau2, &t);
     }
-    inlier_mask[static_cast<size_t>(b) * M + i] = in ? 1 : 0;
+    inlier_mask[row * M + i] = in ? 1 : 0;
     ni += in ? 1 : 0;
     s += t;
   }
@@ -180,14 +179,33 @@ __global__ __launch_bounds__(64) void pnp_polish_kernel(const float* __restrict_
   ni = wave_sum_i(ni);
   if (lane < 16 && ok) {
     const int r = lane >> 2, c = lane & 3;
-    T[16 * b + lane] = r < 3 ? static_cast<float>(Rt[4 * r + c]) : (c == 3 ? 1.f : 0.f);
+    T[16 * row + lane] = r < 3 ? static_cast<float>(Rt[4 * r + c]) : (c == 3 ? 1.f : 0.f);
   }
   if (lane == 0) {
-    best[b] = bh;
-    n_inliers[b] = ok ? ni : 0;
-    final_cost[b] = ok ? s : inf_d();
-    info[b] = ok ? 0 : -1;
+    n_inliers[row] = ok ? ni : 0;
+    final_cost[row] = ok ? s : inf_d();
+    info[row] = ok ? 0 : -1;
+    if (kPol)
+      for (int e = 0; e < 12; ++e) pol[row * 12 + e] = Rt[e];
   }
+}
+
+__global__ __launch_bounds__(64) void pnp_polish_kernel(const float* __restrict__ X, const float* __restrict__ x, const int* __restrict__ count,
+                                                       int M, const float* __restrict__ K, int B, int Hyp, double tau, int n_polish,
+                                                       const HypRec* __restrict__ rec, const double* __restrict__ cost, float* __restrict__ T,
+                                                       int* __restrict__ best, unsigned char* __restrict__ inlier_mask,
+                                                       int* __restrict__ n_inliers, double* __restrict__ final_cost, int* __restrict__ info) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  // the cheapest hypothesis with a cost below +inf, the lowest h on a tie
+  double bc = inf_d();
+  int bh = -1;
+  for (int h = lane; h < Hyp; h += 64) {
+    const double c = cost[static_cast<size_t>(b) * Hyp + h];
+    if (c < inf_d()) better_key(bc, bh, c, h);
+  }
+  for (int o = 32; o >= 1; o >>= 1) better_key(bc, bh, rp::shfl_xor_f64(bc, o), __shfl_xor(bh, o));
+  if (lane == 0) best[b] = bh;
+  polish_body<false>(X, x, count, M, K, b, tau, n_polish, rec, Hyp, bh, b, T, inlier_mask, n_inliers, final_cost, info, nullptr);
 }
 
 inline size_t workspace_bytes(int B, int Hyp) {

@@ -1,7 +1,7 @@
 // The K best DISTINCT hypotheses of the P3P RANSAC.  After pnp_solve_kernel and pnp_score_kernel (csrc/pnp.cuh):
 //   pnp_topk_select_kernel  one workgroup per object: the extent of its correspondences, then Kt greedy rounds -- the cheapest live
 //                           hypothesis (lowest h on a tie), then every hypothesis within `sep` of it dies
-//   pnp_topk_polish_kernel  one wave per (object, slot): what pnp_polish_kernel does for its one hypothesis, statement for statement
+//   pnp_topk_polish_kernel  one wave per (object, slot): the polish body of pnp_polish_kernel (polish_body, csrc/pnp.cuh) on its hypothesis
 //   pnp_topk_dup_kernel     one wave per object: slots whose POLISHED poses lie within `sep` of an earlier polished slot
 // The distance of two poses is the largest displacement of a corner of the extent box.  Thread t of the selection owns the hypotheses
 // h = t (mod 256) in every pass, so the live flags need no synchronisation; minima meet through the fixed xor butterfly and four LDS
@@ -34,13 +34,6 @@ __device__ __forceinline__ double pose_distance(const double* P, const double* Q
     if (n > m || n != n) m = n;                          // (once m is NaN it stays: no later n compares greater)
   }
   return m;
-}
-
-__device__ __forceinline__ void better_key(double& bc, int& bh, double oc, int oh) {
-  if (oh >= 0 && (bh < 0 || oc < bc || (oc == bc && oh < bh))) {
-    bc = oc;
-    bh = oh;
-  }
 }
 
 __global__ __launch_bounds__(kSelThreads) void pnp_topk_select_kernel(const float* __restrict__ X, const int* __restrict__ count, int M, int Hyp,
@@ -100,11 +93,7 @@ __global__ __launch_bounds__(kSelThreads) void pnp_topk_select_kernel(const floa
     int bh = -1;
     for (int h = tid; h < Hyp; h += kSelThreads)
       if (live[row + h]) better_key(bc, bh, cost[row + h], h);
-    for (int o = 32; o >= 1; o >>= 1) {
-      const double oc = rp::shfl_xor_f64(bc, o);
-      const int oh = __shfl_xor(bh, o);
-      better_key(bc, bh, oc, oh);
-    }
+    for (int o = 32; o >= 1; o >>= 1) better_key(bc, bh, rp::shfl_xor_f64(bc, o), __shfl_xor(bh, o));
     __syncthreads();                                     // (the previous round's readers of s_cost / s_h are done)
     if (lane == 0) {
       s_cost[wave] = bc;
@@ -117,21 +106,14 @@ __global__ __launch_bounds__(kSelThreads) void pnp_topk_select_kernel(const floa
     if (bh < 0) break;                                   // (the same in every thread)
     if (tid == 0) hyp[b * Kt + k] = bh;
     ++found;
-    const HypRec* pr = rec + row + bh;
-    const int pb = pr->best;
-    double P[12];
-    for (int e = 0; e < 12; ++e) P[e] = pb >= 0 && pb < 4 ? pr->Rt[pb][e] : __longlong_as_double(0x7ff8000000000000ll);
+    double P[12], Q[12];
+    if (!load_candidate(rec, b, Hyp, bh, P))               // (a pick without a candidate: every distance to it is NaN)
+      for (int e = 0; e < 12; ++e) P[e] = __longlong_as_double(0x7ff8000000000000ll);
     for (int h = tid; h < Hyp; h += kSelThreads) {
       if (!live[row + h]) continue;
-      const HypRec* hr = rec + row + h;
-      const int hb = hr->best;
-      bool keep = hb >= 0 && hb < 4;
+      bool keep = load_candidate(rec, b, Hyp, h, Q);
       if (keep && k == 0) keep = pnpm::finite_d(cost[row + h]) && inliers[row + h] >= min_inliers;      // the gates of the slots k >= 1
-      if (keep) {
-        double Q[12];
-        for (int e = 0; e < 12; ++e) Q[e] = hr->Rt[hb][e];
-        keep = pose_distance(Q, P, lo, hi) > sep;        // must be TRUE: a NaN distance is never distinct; the pick itself has d = 0
-      }
+      if (keep) keep = pose_distance(Q, P, lo, hi) > sep;  // must be TRUE: a NaN distance is never distinct; the pick itself has d = 0
       if (!keep) live[row + h] = 0;
     }
   }
@@ -141,69 +123,15 @@ __global__ __launch_bounds__(kSelThreads) void pnp_topk_select_kernel(const floa
   }
 }
 
-// pnp_polish_kernel's body on the hypothesis hyp[b][k] (-1: none), its outputs at (b, k); the polished pose also goes to `pol` in fp64
+// polish_body (csrc/pnp.cuh) on the hypothesis hyp[b][k] (-1: none), its outputs at (b, k); the polished pose also goes to `pol` in fp64
 __global__ __launch_bounds__(64) void pnp_topk_polish_kernel(const float* __restrict__ X, const float* __restrict__ x, const int* __restrict__ count,
                                                             int M, const float* __restrict__ K, int Hyp, int Kt, double tau, int n_polish,
                                                             const HypRec* __restrict__ rec, const int* __restrict__ hyp, float* __restrict__ T,
                                                             unsigned char* __restrict__ inlier_mask, int* __restrict__ n_inliers,
                                                             double* __restrict__ final_cost, int* __restrict__ info, double* __restrict__ pol) {
-  const int k = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
-  const size_t slot = static_cast<size_t>(b) * Kt + k;
-  const int cnt = clamp_count(count, b, M);
-  const pnpm::Cam cam = load_cam(K, b);
-  const double tau2 = tau * tau;
-  const int bh = hyp[slot];
-  bool ok = bh >= 0 && bh < Hyp;
-  double Rt[12];
-  for (int e = 0; e < 12; ++e) Rt[e] = 0.0;
-  if (ok) {
-    const HypRec* hr = rec + static_cast<size_t>(b) * Hyp + bh;
-    ok = hr->best >= 0 && hr->best < 4;
-    if (ok)
-      for (int e = 0; e < 12; ++e) Rt[e] = hr->Rt[hr->best][e];
-  }
-  for (int it = 0; it < n_polish && ok; ++it) {          // (ok is the same in every lane: the control flow stays wave-uniform)
-    double H[21], g[6];
-    for (int e = 0; e < 21; ++e) H[e] = 0.0;
-    for (int e = 0; e < 6; ++e) g[e] = 0.0;
-    for (int i = lane; i < cnt; i += 64) {
-      double P[3], p[2], r2;
-      load_corr(X, x, static_cast<size_t>(b) * M + i, P, p);
-      if (pnpm::reproj_r2(Rt, cam, P, p, &r2) && r2 < tau2) pnpm::gn_accumulate(Rt, cam, P, p, H, g);
-    }
-    for (int e = 0; e < 21; ++e) H[e] = wave_sum(H[e]);
-    for (int e = 0; e < 6; ++e) g[e] = wave_sum(g[e]);
-    double xi[6];
-    ok = pnpm::chol6_solve(H, g, xi);
-    if (ok) pnpm::se3_left_update(xi, Rt);
-  }
-  for (int e = 0; e < 12; ++e) ok = ok && pnpm::finite_d(Rt[e]);
-  // the final inlier set and MSAC cost, under the final pose
-  double s = 0.0;
-  int ni = 0;
-  for (int i = lane; i < cnt; i += 64) {
-    double P[3], p[2], t = 0.0;
-    bool in = false;
-    if (ok) {
-      load_corr(X, x, static_cast<size_t>(b) * M + i, P, p);
-      in = pnpm::score_point(Rt, cam, P, p, tau2, &t);
-    }
-    inlier_mask[slot * M + i] = in ? 1 : 0;
-    ni += in ? 1 : 0;
-    s += t;
-  }
-  s = wave_sum(s);
-  ni = wave_sum_i(ni);
-  if (lane < 16 && ok) {
-    const int r = lane >> 2, c = lane & 3;
-    T[16 * slot + lane] = r < 3 ? static_cast<float>(Rt[4 * r + c]) : (c == 3 ? 1.f : 0.f);
-  }
-  if (lane == 0) {
-    n_inliers[slot] = ok ? ni : 0;
-    final_cost[slot] = ok ? s : inf_d();
-    info[slot] = ok ? 0 : -1;
-    for (int e = 0; e < 12; ++e) pol[slot * 12 + e] = Rt[e];
-  }
+  const int b = blockIdx.y;
+  const size_t slot = static_cast<size_t>(b) * Kt + blockIdx.x;
+  polish_body<true>(X, x, count, M, K, b, tau, n_polish, rec, Hyp, hyp[slot], slot, T, inlier_mask, n_inliers, final_cost, info, pol);
 }
 
 __global__ __launch_bounds__(64) void pnp_topk_dup_kernel(int Kt, const TopkBox* __restrict__ box, const double* __restrict__ pol,

@@ -2056,6 +2056,26 @@ def raster_occlusion(verts, faces, vert_off, face_off, face_cnt, max_faces, T, K
 DESC_DIM = 32
 
 
+def _source_index(fn, src_index, S, B, dev, what="objects", sources="sources"):
+    """src_index (an ops.SourceIndex, B integers, or None: row b reads source b) -> an ops.SourceIndex over S sources with B entries."""
+    if not isinstance(src_index, SourceIndex):
+        src_index = SourceIndex(range(B) if src_index is None else src_index, S, dev)
+    if src_index.S != S or len(src_index) != B:
+        raise ValueError(f"{fn}: src_index covers {len(src_index)} {what} of {src_index.S} {sources}; there are {B} {what}, {S} {sources}")
+    return src_index
+
+
+def _cached_workspace(cache, key, n_bytes, dtype):
+    """The workspace of `key` (its first entry is the device) in `cache`, n_bytes of 8-byte `dtype` elements; at most 8 keys are kept,
+    the oldest leaves first."""
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) >= 8:
+            cache.pop(next(iter(cache)))
+        ws = cache[key] = torch.empty(n_bytes // 8, device=key[0], dtype=dtype)
+    return ws
+
+
 def _point_offsets(pt_off, total, max_points, device):
     """-> (device int32 (B+1,), B, largest count).  A host sequence is checked here (ascending, inside [0, total]); a device tensor is
     taken as it is, with max_points from the caller (the kernel gives count = 0 to an object whose range does not fit)."""
@@ -2101,12 +2121,7 @@ def desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=
     pt_off, B, largest = _point_offsets(pt_off, total, max_points, dev)
     if not 1 <= largest <= total:
         raise ValueError(f"desc_match: max_points must lie in [1, {total}], got {largest}")
-    if src_index is None:
-        src_index = range(B)
-    if not isinstance(src_index, SourceIndex):
-        src_index = SourceIndex(src_index, S, dev)
-    if src_index.S != S or len(src_index) != B:
-        raise ValueError(f"desc_match: src_index covers {len(src_index)} objects of {src_index.S} sources; there are {B} objects, {S} sources")
+    src_index = _source_index("desc_match", src_index, S, B, dev, "objects", "sources")
     if not isinstance(bbox, torch.Tensor) or not bbox.is_cuda:
         bbox = torch.as_tensor(bbox, dtype=torch.int32).to(dev)
     _i32_dev(bbox, "bbox")
@@ -2144,6 +2159,38 @@ def random_words(rnd):
     return rnd.contiguous()
 
 
+def _pnp_inputs(fn, X, x, count, K, rnd, tau, n_polish, min_count):
+    """The inputs of `pnp_ransac` and `pnp_ransac_topk`, checked (ValueError) and as the library takes them: K per object, rnd as int32
+    words.  -> (X, x, count, K, rnd, B, M, Hyp, tau, n_polish, min_count, dev)."""
+    for t, nm in ((X, "X"), (x, "x"), (K, "K")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype.is_floating_point):
+            raise ValueError(f"{fn}: {nm} must be a floating-point GPU tensor")
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
+        raise ValueError(f"{fn}: count must be a contiguous int32 GPU tensor")
+    X, x, K = _chk(X, "X"), _chk(x, "x"), _chk(K, "K")
+    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"{fn}: X must be (B,M,3), got {tuple(X.shape)}")
+    B, M = X.shape[0], X.shape[1]
+    if x.shape != (B, M, 2):
+        raise ValueError(f"{fn}: x must be ({B},{M},2), got {tuple(x.shape)}")
+    if count.shape != (B,):
+        raise ValueError(f"{fn}: count must be ({B},), got {tuple(count.shape)}")
+    if K.shape == (3, 3):
+        K = K.expand(B, 3, 3).contiguous()
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"{fn}: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
+    rnd = random_words(rnd)
+    if not rnd.is_cuda or rnd.dim() != 3 or rnd.shape[0] != B or rnd.shape[2] != 3 or rnd.shape[1] < 1:
+        raise ValueError(f"{fn}: rnd must be a GPU tensor of shape ({B},Hyp,3), got {tuple(rnd.shape)} on {rnd.device}")
+    if not (X.device == x.device == count.device == K.device == rnd.device):
+        raise ValueError(f"{fn}: all tensors must live on one device")
+    Hyp = rnd.shape[1]
+    tau, n_polish, min_count = float(tau), int(n_polish), int(min_count)
+    if not (tau > 0.0 and tau < float("inf")) or not 0 <= n_polish <= 64 or min_count < 4:
+        raise ValueError(f"{fn}: tau > 0 and finite, n_polish in [0,64], min_count >= 4; got {tau}, {n_polish}, {min_count}")
+    return X, x, count, K, rnd, B, M, Hyp, tau, n_polish, min_count, X.device
+
+
 def pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, T=None):
     """P3P RANSAC with MSAC scoring and a Gauss-Newton polish, fp64 on the device (rnnpose_pnp_ransac_f64).  X (B,M,3), x (B,M,2),
     count (B) int32: the matcher's outputs; K (3,3) or (B,3,3); rnd (B,Hyp,3) random 32-bit words (ops.random_words): hypothesis h of
@@ -2152,33 +2199,12 @@ def pnp_ransac(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, T=None):
     -> T (B,4,4), cost (B,Hyp) fp64, inliers (B,Hyp) int32, best (B) int32, inlier_mask (B,M) uint8, n_inliers (B) int32,
        final_cost (B) fp64, info (B) int32 (0, or -1: too few correspondences / no candidate / singular polish).
     Shapes, dtypes and devices are checked here, on the host (ValueError)."""
-    X, x, K = _chk(X, "X"), _chk(x, "x"), _chk(K, "K")
-    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError(f"pnp_ransac: X must be (B,M,3), got {tuple(X.shape)}")
-    B, M = X.shape[0], X.shape[1]
-    if x.shape != (B, M, 2):
-        raise ValueError(f"pnp_ransac: x must be ({B},{M},2), got {tuple(x.shape)}")
-    _i32_dev(count, "count")
-    if count.shape != (B,):
-        raise ValueError(f"pnp_ransac: count must be ({B},), got {tuple(count.shape)}")
-    if K.shape == (3, 3):
-        K = K.expand(B, 3, 3).contiguous()
-    if K.shape != (B, 3, 3):
-        raise ValueError(f"pnp_ransac: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
-    rnd = random_words(rnd)
-    if not rnd.is_cuda or rnd.dim() != 3 or rnd.shape[0] != B or rnd.shape[2] != 3 or rnd.shape[1] < 1:
-        raise ValueError(f"pnp_ransac: rnd must be a GPU tensor of shape ({B},Hyp,3), got {tuple(rnd.shape)} on {rnd.device}")
-    if not (X.device == x.device == count.device == K.device == rnd.device):
-        raise ValueError("pnp_ransac: all tensors must live on one device")
-    Hyp = rnd.shape[1]
-    tau, n_polish, min_count = float(tau), int(n_polish), int(min_count)
-    if not (tau > 0.0 and tau < float("inf")) or not 0 <= n_polish <= 64 or min_count < 4:
-        raise ValueError(f"pnp_ransac: tau > 0 and finite, n_polish in [0,64], min_count >= 4; got {tau}, {n_polish}, {min_count}")
-    dev = X.device
+    fn = "pnp_ransac"
+    X, x, count, K, rnd, B, M, Hyp, tau, n_polish, min_count, dev = _pnp_inputs(fn, X, x, count, K, rnd, tau, n_polish, min_count)
     if T is None:
         T = torch.eye(4, device=dev, dtype=F32).repeat(B, 1, 1)
     elif not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == F32 and T.is_contiguous() and tuple(T.shape) == (B, 4, 4)):
-        raise ValueError(f"pnp_ransac: T must be a contiguous fp32 GPU tensor of shape ({B},4,4)")
+        raise ValueError(f"{fn}: T must be a contiguous fp32 GPU tensor of shape ({B},4,4)")
     n = int(_lib.load().rnnpose_pnp_ransac_workspace_bytes(B, Hyp))
     ws = torch.empty(n // 8, device=dev, dtype=torch.int64)
     cost = torch.empty(B, Hyp, device=dev, dtype=F64)
@@ -2209,36 +2235,11 @@ def pnp_ransac_topk(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, top_k
     Shapes, dtypes, devices, contiguity and ranges are checked here, on the host (ValueError).  The workspace is cached per
     (device, B, Hyp, top_k): calls of one shape must not overlap on different streams."""
     fn = "pnp_ransac_topk"
-    for t, nm in ((X, "X"), (x, "x"), (K, "K")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype.is_floating_point):
-            raise ValueError(f"{fn}: {nm} must be a floating-point GPU tensor")
-    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
-        raise ValueError(f"{fn}: count must be a contiguous int32 GPU tensor")
-    X, x, K = _chk(X, "X"), _chk(x, "x"), _chk(K, "K")
-    if X.dim() != 3 or X.shape[2] != 3 or X.shape[0] < 1 or X.shape[1] < 1:
-        raise ValueError(f"{fn}: X must be (B,M,3), got {tuple(X.shape)}")
-    B, M = X.shape[0], X.shape[1]
-    if x.shape != (B, M, 2):
-        raise ValueError(f"{fn}: x must be ({B},{M},2), got {tuple(x.shape)}")
-    if count.shape != (B,):
-        raise ValueError(f"{fn}: count must be ({B},), got {tuple(count.shape)}")
-    if K.shape == (3, 3):
-        K = K.expand(B, 3, 3).contiguous()
-    if K.shape != (B, 3, 3):
-        raise ValueError(f"{fn}: K must be (3,3) or ({B},3,3), got {tuple(K.shape)}")
-    rnd = random_words(rnd)
-    if not rnd.is_cuda or rnd.dim() != 3 or rnd.shape[0] != B or rnd.shape[2] != 3 or rnd.shape[1] < 1:
-        raise ValueError(f"{fn}: rnd must be a GPU tensor of shape ({B},Hyp,3), got {tuple(rnd.shape)} on {rnd.device}")
-    if not (X.device == x.device == count.device == K.device == rnd.device):
-        raise ValueError(f"{fn}: all tensors must live on one device")
-    Hyp = rnd.shape[1]
-    tau, n_polish, min_count, sep_frac = float(tau), int(n_polish), int(min_count), float(sep_frac)
-    if not (tau > 0.0 and tau < float("inf")) or not 0 <= n_polish <= 64 or min_count < 4:
-        raise ValueError(f"{fn}: tau > 0 and finite, n_polish in [0,64], min_count >= 4; got {tau}, {n_polish}, {min_count}")
+    X, x, count, K, rnd, B, M, Hyp, tau, n_polish, min_count, dev = _pnp_inputs(fn, X, x, count, K, rnd, tau, n_polish, min_count)
+    sep_frac = float(sep_frac)
     if int(top_k) != top_k or not 1 <= int(top_k) <= PNP_TOPK_MAX or not 0.0 <= sep_frac < float("inf") or int(min_inliers) != min_inliers or min_inliers < 0:
         raise ValueError(f"{fn}: top_k in [1,{PNP_TOPK_MAX}], sep_frac >= 0 and finite, min_inliers >= 0; got {top_k}, {sep_frac}, {min_inliers}")
     Kt, min_inliers = int(top_k), int(min_inliers)
-    dev = X.device
     if T is None:
         T = torch.eye(4, device=dev, dtype=F32).repeat(B, Kt, 1, 1)
     elif not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == F32 and T.is_contiguous() and tuple(T.shape) == (B, Kt, 4, 4) and T.device == dev):
@@ -2246,12 +2247,7 @@ def pnp_ransac_topk(X, x, count, K, rnd, tau=4.0, n_polish=4, min_count=4, top_k
     n = int(_lib.load().rnnpose_pnp_ransac_topk_workspace_bytes(B, Hyp, Kt))
     if n == 0 or B * M * Kt >= 2 ** 31:
         raise ValueError(f"{fn}: {B} objects x {Hyp} hypotheses x {Kt} slots x {M} correspondences are more than one call takes")
-    key = (dev, B, Hyp, Kt)
-    ws = _topk_ws.get(key)
-    if ws is None:
-        if len(_topk_ws) >= 8:
-            _topk_ws.pop(next(iter(_topk_ws)))
-        ws = _topk_ws[key] = torch.empty(n // 8, device=dev, dtype=torch.int64)
+    ws = _cached_workspace(_topk_ws, (dev, B, Hyp, Kt), n, torch.int64)
     cost = torch.empty(B, Hyp, device=dev, dtype=F64)
     inliers = torch.empty(B, Hyp, device=dev, dtype=torch.int32)
     hyp = torch.empty(B, Kt, device=dev, dtype=torch.int32)
@@ -2309,12 +2305,7 @@ def pose_score(rend_depth, rend_desc, window, desc2d, src_index=None, depth_obs=
     _strict(window, "window", torch.int32, fn)
     if tuple(window.shape) != (B, 2):
         raise ValueError(f"{fn}: window must be ({B}, 2), got {tuple(window.shape)}")
-    if src_index is None:
-        src_index = range(B)
-    if not isinstance(src_index, SourceIndex):
-        src_index = SourceIndex(src_index, S, dev)
-    if src_index.S != S or len(src_index) != B:
-        raise ValueError(f"{fn}: src_index covers {len(src_index)} poses of {src_index.S} frames; there are {B} poses, {S} frames")
+    src_index = _source_index(fn, src_index, S, B, dev, "poses", "frames")
     if any(t.device != dev for t in (rend_depth, desc2d, window, src_index.dev) + (() if depth_obs is None else (depth_obs,))):
         raise ValueError(f"{fn}: all tensors must live on one device")
     depth_tol = float(depth_tol)
@@ -2323,12 +2314,7 @@ def pose_score(rend_depth, rend_desc, window, desc2d, src_index=None, depth_obs=
     n = int(_lib.load().rnnpose_pose_score_workspace_bytes(B, h, w))
     if n == 0:
         raise ValueError(f"{fn}: {B} windows of {h} x {w} pixels are more than one call takes")
-    key = (dev, B, h, w)
-    ws = _score_ws.get(key)
-    if ws is None:
-        if len(_score_ws) >= 8:
-            _score_ws.pop(next(iter(_score_ws)))
-        ws = _score_ws[key] = torch.empty(n // 8, device=dev, dtype=F64)
+    ws = _cached_workspace(_score_ws, (dev, B, h, w), n, F64)
     stats = torch.empty(B, len(POSE_SCORE_COLUMNS), device=dev, dtype=F64)
     score = torch.empty(B, device=dev, dtype=F64)
     _launch("rnnpose_pose_score_f64", _ptr(rend_depth), _ptr(rend_desc), _ptr(window), _ptr(desc2d), _ptr(depth_obs), _ptr(src_index.dev), B, S,

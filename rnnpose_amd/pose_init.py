@@ -103,6 +103,20 @@ class DescriptorPoseInitializer:
             bboxes = torch.as_tensor(np.asarray(bboxes).astype(np.int32).reshape(B, 4))
         return geofea_2d, Kt, bboxes.to(self.device, torch.int32).contiguous()
 
+    def _record(self, T, valid, names, Kt, bboxes, size, **tensors):
+        """The host record of a call: the device `tensors` as numpy arrays, valid = valid(record) (B) or (B,top_k), and fallback (B):
+        True where an object has nothing valid.  Those objects get their box-centre start (`fallback`) written into T (B,4,4), a view
+        of the poses on the device."""
+        rec = {k: t.cpu().numpy() for k, t in tensors.items()}
+        rec["valid"] = valid(rec)
+        rec["fallback"] = ~rec["valid"].reshape(len(names), -1).any(1)
+        if rec["fallback"].any():
+            Kh, bh = Kt.cpu().numpy(), bboxes.cpu().numpy()
+            rows = np.nonzero(rec["fallback"])[0]
+            fb = np.stack([self.fallback(names[j], Kh[j], bh[j], size) for j in rows])
+            T[torch.as_tensor(rows, device=self.device)] = torch.as_tensor(fb).to(self.device)
+        return rec
+
     def __call__(self, names, geofea_2d, image_index, K, bboxes):
         """names: B class names; geofea_2d (S,32,H,W) on the device; image_index: B integers (which map every object reads), an
         ops.SourceIndex or None (object b reads map b); K (3,3) or (B,3,3); bboxes (B,4) [xmin, ymin, xmax, ymax] inclusive pixels
@@ -113,13 +127,8 @@ class DescriptorPoseInitializer:
         geofea_2d, Kt, bboxes = self._inputs(B, geofea_2d, K, bboxes)
         X, x, _, _, count = self.match(names, geofea_2d, image_index, bboxes)
         T, _, _, _, _, n_inl, fcost, info = ops.pnp_ransac(X, x, count, Kt, self.random_words(B), self.tau, self.n_polish, self.min_count)
-        rec = dict(count=count.cpu().numpy(), n_inliers=n_inl.cpu().numpy(), final_cost=fcost.cpu().numpy(), info=info.cpu().numpy())
-        rec["fallback"] = rec["info"] != 0
-        if rec["fallback"].any():
-            Kh, bh = Kt.cpu().numpy(), bboxes.cpu().numpy()
-            rows = np.nonzero(rec["fallback"])[0]
-            fb = np.stack([self.fallback(names[j], Kh[j], bh[j], geofea_2d.shape[-2:]) for j in rows])
-            T[torch.as_tensor(rows, device=self.device)] = torch.as_tensor(fb).to(self.device)
+        rec = self._record(T, lambda r: r["info"] == 0, names, Kt, bboxes, geofea_2d.shape[-2:], count=count, n_inliers=n_inl, final_cost=fcost, info=info)
+        del rec["valid"]                                     # (one slot: fallback says it all)
         return T, rec
 
     def candidates(self, names, geofea_2d, image_index, K, bboxes):
@@ -132,15 +141,8 @@ class DescriptorPoseInitializer:
         X, x, _, _, count = self.match(names, geofea_2d, image_index, bboxes)
         T, _, _, hyp, _, n_inl, fcost, info, dup_of, n_found = ops.pnp_ransac_topk(
             X, x, count, Kt, self.random_words(B), self.tau, self.n_polish, self.min_count, self.top_k, self.sep_frac, self.min_inliers)
-        rec = dict(count=count.cpu().numpy(), hyp=hyp.cpu().numpy(), n_inliers=n_inl.cpu().numpy(), final_cost=fcost.cpu().numpy(),
-                   info=info.cpu().numpy(), dup_of=dup_of.cpu().numpy(), n_found=n_found.cpu().numpy())
-        rec["valid"] = (rec["info"] == 0) & (rec["dup_of"] < 0)
-        rec["fallback"] = ~rec["valid"].any(1)
-        if rec["fallback"].any():
-            Kh, bh = Kt.cpu().numpy(), bboxes.cpu().numpy()
-            rows = np.nonzero(rec["fallback"])[0]
-            fb = np.stack([self.fallback(names[j], Kh[j], bh[j], geofea_2d.shape[-2:]) for j in rows])
-            T[torch.as_tensor(rows, device=self.device), 0] = torch.as_tensor(fb).to(self.device)
+        rec = self._record(T[:, 0], lambda r: (r["info"] == 0) & (r["dup_of"] < 0), names, Kt, bboxes, geofea_2d.shape[-2:], count=count, hyp=hyp,
+                           n_inliers=n_inl, final_cost=fcost, info=info, dup_of=dup_of, n_found=n_found)
         # (the copy comes from the FIRST valid slot: slot 0, unless its own polish failed where a later slot's did not)
         first = torch.as_tensor(rec["valid"].argmax(1)).to(self.device)
         src = T[torch.arange(B, device=self.device), first][:, None]

@@ -90,9 +90,11 @@ EXTRA = ["runtime_host.cpp"]
 # next to scratch copies of those sources (quote includes look there first)
 MUTABLE_HEADERS = {"corr_lookup.cuh": ["corr_lookup.hip", "corr_convc1.hip"], "resident_tile.cuh": ["conv1x1_resident.hip", "corr_convc1.hip"],
                    "conv_common.cuh": ["conv_igemm.hip"],          # (+ the strip sources, which are scratch copies next to their patched header anyway)
-                   "f16x3.cuh": ["nhwc_ops.hip", "stem.hip", "mask_upsample.hip", "corr_pyramid.hip", "conv_igemm.hip", "conv1x1_resident.hip", "corr_convc1.hip"]}
+                   "f16x3.cuh": ["nhwc_ops.hip", "stem.hip", "mask_upsample.hip", "corr_pyramid.hip", "conv_igemm.hip", "conv1x1_resident.hip", "corr_convc1.hip"],
+                   "pnp.cuh": ["eval_metrics.hip"], "pnp_topk.cuh": ["eval_metrics.hip"], "pnp_math.cuh": ["eval_metrics.hip"],
+                   "desc_match.cuh": ["eval_metrics.hip"], "pose_score.cuh": ["eval_metrics.hip"]}
 # a mutated header that other headers include: those are copied next to it, so that THEIR quote include finds the mutated copy too
-HEADER_COMPANIONS = {"f16x3.cuh": ["conv_common.cuh", "resident_tile.cuh"]}
+HEADER_COMPANIONS = {"f16x3.cuh": ["conv_common.cuh", "resident_tile.cuh"], "pnp.cuh": ["pnp_topk.cuh"], "pnp_math.cuh": ["pnp.cuh", "pnp_topk.cuh"]}
 
 
 def clang() -> str:

@@ -175,10 +175,16 @@ def jacobian(R, t, K, X, x):
     return uv - np.asarray(x, np.float64), Jp @ JT
 
 
-def polish(R, t, K, X, x, tau, n_polish):
-    """n_polish Gauss-Newton steps, the inlier set re-selected with tau before every step -> (R, t) or None (system not positive definite)."""
+def polish(R, t, K, X, x, tau, n_polish, margins=None):
+    """n_polish Gauss-Newton steps, the inlier set re-selected with tau before every step -> (R, t), or None (no inlier, a system that
+    is not positive definite, a pose that is not finite).  margins: a list that receives the smallest | |r| - tau | of every inlier
+    decision taken on the way and of the one the final pose's mask will take (nothing where no residual is finite)."""
+    def note(r2):
+        if margins is not None and np.isfinite(r2).any():
+            margins.append(float(np.abs(np.sqrt(r2[np.isfinite(r2)]) - tau).min()))
+        return r2
     for _ in range(n_polish):
-        m = residuals2(R, t, K, X, x) < tau * tau
+        m = note(residuals2(R, t, K, X, x)) < tau * tau
         if not m.any():
             return None
         r, J = jacobian(R, t, K, X[m], x[m])
@@ -192,21 +198,27 @@ def polish(R, t, K, X, x, tau, n_polish):
             return None
         xi = -np.linalg.solve(L.T, np.linalg.solve(L, g))
         R, t = left_update(xi, R, t)
+    if not (np.all(np.isfinite(R)) and np.all(np.isfinite(t))):
+        return None
+    note(residuals2(R, t, K, X, x))
     return R, t
 
 
-def ransac_object(X, x, count, K, rnd, tau, n_polish, min_count):
-    """One object: X (M,3), x (M,2), rnd (Hyp,3) uint32.  -> dict cost (Hyp), inliers (Hyp), best, T (4,4) or None, inlier_mask (count),
-    n_inliers, final_cost, info, and r2_final (the squared residuals under the final pose)."""
-    Hyp = rnd.shape[0]
-    count = int(count)
-    X, x = np.asarray(X, np.float64)[:count], np.asarray(x, np.float64)[:count]
-    cost, inl = np.full(Hyp, np.inf), np.zeros(Hyp, np.int64)
-    poses = [None] * Hyp
-    out = dict(cost=cost, inliers=inl, best=-1, T=None, inlier_mask=np.zeros(count, bool), n_inliers=0, final_cost=np.inf, info=-1, r2_final=None)
-    if count < min_count:
-        return out
-    Kd = np.asarray(K, np.float64)
+def pose_matrix(R, t):
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return T
+
+
+def hypotheses(X, x, count, K, rnd, tau, min_count=4):
+    """One object: X (M,3), x (M,2), rnd (Hyp,3) uint32; count is clamped to [0, M] as the kernels clamp it.  Hypothesis h samples the
+    correspondences rnd[h] % count; its cheapest P3P solution is its candidate.
+    -> cost (Hyp), inliers (Hyp), poses (list of (4,4) or None)."""
+    Hyp, count = rnd.shape[0], max(0, min(int(count), len(X)))
+    X, x, Kd = np.asarray(X, np.float64)[:count], np.asarray(x, np.float64)[:count], np.asarray(K, np.float64)
+    cost, inl, poses = np.full(Hyp, np.inf), np.zeros(Hyp, np.int64), [None] * Hyp
+    if count < min_count or count < 3:
+        return cost, inl, poses
     for h in range(Hyp):
         i = [int(r) % count for r in rnd[h]]
         if len(set(i)) < 3:
@@ -215,19 +227,26 @@ def ransac_object(X, x, count, K, rnd, tau, n_polish, min_count):
         for R, t in p3p(X[i], xn):
             c, n, _ = score(R, t, Kd, X, x, tau)
             if c < cost[h]:
-                cost[h], inl[h], poses[h] = c, n, (R, t)
+                cost[h], inl[h], poses[h] = c, n, pose_matrix(R, t)
+    return cost, inl, poses
+
+
+def ransac_object(X, x, count, K, rnd, tau, n_polish, min_count):
+    """One object (the arguments of `hypotheses`).  -> dict cost (Hyp), inliers (Hyp), best, T (4,4) or None, inlier_mask (count),
+    n_inliers, final_cost, info, and r2_final (the squared residuals under the final pose)."""
+    cost, inl, poses = hypotheses(X, x, count, K, rnd, tau, min_count)
+    count = max(0, min(int(count), len(X)))
+    X, x, Kd = np.asarray(X, np.float64)[:count], np.asarray(x, np.float64)[:count], np.asarray(K, np.float64)
+    out = dict(cost=cost, inliers=inl, best=-1, T=None, inlier_mask=np.zeros(count, bool), n_inliers=0, final_cost=np.inf, info=-1, r2_final=None)
     if not np.isfinite(cost).any():
         return out
     best = int(np.argmin(cost))              # the first minimum: the lowest h on a tie
     out["best"] = best
-    pose = polish(*poses[best], Kd, X, x, tau, n_polish)
-    if pose is None or not (np.all(np.isfinite(pose[0])) and np.all(np.isfinite(pose[1]))):
+    pose = polish(poses[best][:3, :3], poses[best][:3, 3], Kd, X, x, tau, n_polish)
+    if pose is None:
         return out
-    R, t = pose
-    c, n, m = score(R, t, Kd, X, x, tau)
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    out.update(T=T, inlier_mask=m, n_inliers=n, final_cost=c, info=0, r2_final=residuals2(R, t, Kd, X, x))
+    c, n, m = score(*pose, Kd, X, x, tau)
+    out.update(T=pose_matrix(*pose), inlier_mask=m, n_inliers=n, final_cost=c, info=0, r2_final=residuals2(*pose, Kd, X, x))
     return out
 
 

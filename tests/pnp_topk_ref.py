@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 import pnp_ref as pr
+from pnp_ref import hypotheses, pose_matrix          # (this module's users reach them here)
 
 
 def extent(X, count):
@@ -31,31 +32,6 @@ def distance(P, Q, lo, hi):
     P, Q, C = np.asarray(P, np.float64), np.asarray(Q, np.float64), corners(lo, hi)
     a, b = C @ P[:3, :3].T + P[:3, 3], C @ Q[:3, :3].T + Q[:3, 3]
     return float(np.max(np.sqrt(((a - b) ** 2).sum(1))))
-
-
-def pose_matrix(R, t):
-    T = np.eye(4)
-    T[:3, :3], T[:3, 3] = R, t
-    return T
-
-
-def hypotheses(X, x, count, K, rnd, tau, min_count=4):
-    """One object: pnp_ref.ransac_object's hypothesis loop.  -> cost (Hyp), inliers (Hyp), poses (list of (4,4) or None)."""
-    Hyp, count = rnd.shape[0], max(0, min(int(count), len(X)))
-    X, x, Kd = np.asarray(X, np.float64)[:count], np.asarray(x, np.float64)[:count], np.asarray(K, np.float64)
-    cost, inl, poses = np.full(Hyp, np.inf), np.zeros(Hyp, np.int64), [None] * Hyp
-    if count < min_count or count < 3:
-        return cost, inl, poses
-    for h in range(Hyp):
-        i = [int(r) % count for r in rnd[h]]
-        if len(set(i)) < 3:
-            continue
-        xn = np.stack([(x[i, 0] - Kd[0, 2]) / Kd[0, 0], (x[i, 1] - Kd[1, 2]) / Kd[1, 1]], 1)
-        for R, t in pr.p3p(X[i], xn):
-            c, n, _ = pr.score(R, t, Kd, X, x, tau)
-            if c < cost[h]:
-                cost[h], inl[h], poses[h] = c, n, pose_matrix(R, t)
-    return cost, inl, poses
 
 
 def select(cost, inliers, poses, lo, hi, sep, Kt, min_inliers=0):
@@ -83,35 +59,6 @@ def select(cost, inliers, poses, lo, hi, sep, Kt, min_inliers=0):
     return chosen, margin
 
 
-def polish_slot(T0, K, X, x, tau, n_polish):
-    """pnp_ref.polish with a record: -> ((R, t) or None, the smallest | |r| - tau | over every inlier decision taken on the way)."""
-    R, t = np.asarray(T0, np.float64)[:3, :3], np.asarray(T0, np.float64)[:3, 3]
-    margin = np.inf
-
-    def note(r2):
-        f = np.isfinite(r2)
-        return min(margin, float(np.abs(np.sqrt(r2[f]) - tau).min())) if f.any() else margin
-    for _ in range(n_polish):
-        r2 = pr.residuals2(R, t, K, X, x)
-        margin = note(r2)
-        m = r2 < tau * tau
-        if not m.any():
-            return None, margin
-        r, J = pr.jacobian(R, t, K, X[m], x[m])
-        J2, rr = J.reshape(-1, 6), r.reshape(-1)
-        H, g = J2.T @ J2, J2.T @ rr
-        try:
-            L = np.linalg.cholesky(H)
-        except np.linalg.LinAlgError:
-            return None, margin
-        if np.any(np.diag(L) ** 2 <= 1e-13 * np.diag(H)):
-            return None, margin
-        R, t = pr.left_update(-np.linalg.solve(L.T, np.linalg.solve(L, g)), R, t)
-    if not (np.all(np.isfinite(R)) and np.all(np.isfinite(t))):
-        return None, margin
-    return (R, t), note(pr.residuals2(R, t, K, X, x))
-
-
 def topk_object(X, x, count, K, rnd, tau, n_polish, min_count, Kt, sep_frac, min_inliers=0, hyps=None, cost=None, inliers=None):
     """One object.  hyps: (cost, inliers, poses) of `hypotheses` computed before (None: computed here); cost / inliers: arrays that
     REPLACE the restatement's in the selection (the device's).
@@ -129,8 +76,9 @@ def topk_object(X, x, count, K, rnd, tau, n_polish, min_count, Kt, sep_frac, min
                info=np.full(Kt, -1, np.int64), dup_of=np.full(Kt, -1, np.int64), select_margin=smargin, dup_margin=np.inf, tau_margin=np.inf)
     for k, h in enumerate(chosen):
         out["hyp"][k] = h
-        pose, tm = polish_slot(poses[h], Kd, Xd, xd, tau, n_polish)
-        out["tau_margin"] = min(out["tau_margin"], tm)
+        tm = []
+        pose = pr.polish(poses[h][:3, :3], poses[h][:3, 3], Kd, Xd, xd, tau, n_polish, margins=tm)
+        out["tau_margin"] = min([out["tau_margin"]] + tm)
         if pose is None:
             continue
         c, n, m = pr.score(*pose, Kd, Xd, xd, tau)

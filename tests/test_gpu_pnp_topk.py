@@ -193,6 +193,33 @@ def run_ops(ops, case, Hyp=None, **kw):
     return dict(zip(("T", "cost", "inliers", "hyp", "mask", "n_inl", "fcost", "info", "dup_of", "n_found"), out))
 
 
+def test_every_slot_is_pnp_ransac_on_its_own_hypothesis(ops, grid_ref):
+    """Slot k of every output is bit-identical to ops.pnp_ransac called with slot k's hypothesis as its ONLY one (rnd[b, hyp[b, k]]):
+    with one hypothesis that call picks it, and both entry points polish with the one body (polish_body, csrc/pnp.cuh).  Against a
+    vacuous pass: every object fills at least two slots, on the restatement first."""
+    case, hyps = grid_ref
+    X, x, counts, K, rnd = case[:5]
+    Hyp, Kt = 65, 4
+    assert all(r["n_found"] >= 2 for r in restate(case, hyps, Hyp, Kt)), "the planted case no longer fills two slots per object"
+    o = run_ops(ops, case, Hyp=Hyp, top_k=Kt, T=torch.full((3, Kt, 4, 4), -777.0).cuda())
+    hyp = o["hyp"].long()
+    assert bool(((hyp >= 0).sum(1) >= 2).all()), hyp
+    a, w, compared = (dev(X), dev(x), dev(counts, np.int32), dev(K)), words(rnd[:, :Hyp]), 0
+    for k in range(Kt):
+        rows = hyp[:, k] >= 0                                # (objects without a slot k: their hypothesis 0 runs and is not compared)
+        h = hyp[:, k].clamp(min=0)
+        one = w[torch.arange(3).cuda(), h][:, None].contiguous()
+        T1, cost1, inl1, best, mask1, n1, f1, info1 = ops.pnp_ransac(*a, one, tau=TAU, n_polish=N_POLISH, T=torch.full((3, 4, 4), -777.0).cuda())
+        assert tuple(one.shape) == (3, 1, 3) and bool((best[rows] == 0).all())
+        assert torch.equal(cost1[rows, 0], o["cost"][rows, h[rows]]) and torch.equal(inl1[rows, 0], o["inliers"][rows, h[rows]])
+        assert torch.equal(mask1[rows], o["mask"][rows, k]) and torch.equal(n1[rows], o["n_inl"][rows, k])
+        assert torch.equal(f1[rows], o["fcost"][rows, k]) and torch.equal(info1[rows], o["info"][rows, k])
+        written = rows & (info1 == 0)
+        assert torch.equal(T1[written], o["T"][written, k])
+        compared += int(rows.sum())
+    assert compared >= 6 and compared == int((hyp >= 0).sum())
+
+
 def test_two_modes_fill_slots_0_and_1(ops, grid_ref):
     case, _ = grid_ref
     Ta, Tb = case[5], case[6]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "host_exec"))
 
 SELECT_K = "not end_to_end and not torch_ops"
-EXPECTED = 4 * 4 + 4 + 1 + 1 + 1 + 1 + 1 + 1 + 1 + 1      # the grid, slot 0 per Kt, two modes, gates, fewer modes, degenerate, one optimum, reruns / batch, bad arguments, ops refusals
+EXPECTED = 4 * 4 + 4 + 1 + 1 + 1 + 1 + 1 + 1 + 1 + 1 + 1      # the grid, slot 0 per Kt, every slot, two modes, gates, fewer modes, degenerate, one optimum, reruns / batch, bad arguments, ops refusals
 
 
 def test_pnp_topk_gpu_tests_pass_on_the_host_executed_kernels(tmp_path_factory):
