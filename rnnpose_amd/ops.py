@@ -1742,9 +1742,14 @@ def radius_neighbors(queries, supports, q_lengths, s_lengths, radius: float, lim
 
 # ---- f2/f3: evaluator metrics ------------------------------------------------------------------------------------
 def nn_search(ref_pts, que_pts, exclude_self: bool = False):
-    """ref (B,N1,D), que (B,N2,D) fp32 on the GPU, D in {2,3} -> idx (B,N2) int32: first nearest reference point."""
+    """ref (B,N1,D), que (B,N2,D) fp32 on the GPU, D in {2,3} -> idx (B,N2) int32: first nearest reference point.
+    Shapes are checked here (ValueError); nothing is launched then."""
     ref_pts, que_pts = _chk(ref_pts, "ref_pts"), _chk(que_pts, "que_pts")
+    if ref_pts.dim() != 3 or ref_pts.shape[2] not in (2, 3) or ref_pts.shape[0] < 1 or ref_pts.shape[1] < 1:
+        raise ValueError(f"nn_search: ref_pts must be (B,N1,D) with B, N1 >= 1 and D in (2, 3), got {tuple(ref_pts.shape)}")
     B, n1, dim = ref_pts.shape
+    if que_pts.dim() != 3 or que_pts.shape[0] != B or que_pts.shape[2] != dim or que_pts.shape[1] < 1:
+        raise ValueError(f"nn_search: que_pts must be ({B},N2,{dim}) with N2 >= 1, as ref_pts {tuple(ref_pts.shape)}, got {tuple(que_pts.shape)}")
     n2 = que_pts.shape[1]
     idx = torch.empty(B, n2, device=ref_pts.device, dtype=torch.int32)
     _launch("rnnpose_nn_search_f32", _ptr(ref_pts), _ptr(que_pts), _ptr(idx), B, n1, n2, dim, int(exclude_self), _stream())
@@ -1753,8 +1758,16 @@ def nn_search(ref_pts, que_pts, exclude_self: bool = False):
 
 def pose_metrics(model, pose_pred, pose_gt, K, symmetric: bool = False):
     """model (P,3), pose_pred/pose_gt (B,3,4), K (3,3) -> (B,5) fp64 [ADD, ADD-S (-1 if not symmetric), proj2d px,
-    translation cm, rotation deg]   (utils/eval_metric.py:102-192)."""
+    translation cm, rotation deg]   (utils/eval_metric.py:102-192).  Shapes are checked here (ValueError); nothing is launched then."""
     model, pose_pred, pose_gt, K = _chk(model, "model"), _chk(pose_pred, "pose_pred"), _chk(pose_gt, "pose_gt"), _chk(K, "K")
+    if model.dim() != 2 or model.shape[1] != 3 or model.shape[0] < 1:
+        raise ValueError(f"pose_metrics: model must be (P,3) with P >= 1, got {tuple(model.shape)}")
+    if pose_pred.dim() != 3 or pose_pred.shape[1:] != (3, 4) or pose_pred.shape[0] < 1:
+        raise ValueError(f"pose_metrics: pose_pred must be (B,3,4) with B >= 1, got {tuple(pose_pred.shape)}")
+    if pose_gt.shape != pose_pred.shape:
+        raise ValueError(f"pose_metrics: pose_gt must be {tuple(pose_pred.shape)}, as pose_pred, got {tuple(pose_gt.shape)}")
+    if K.shape != (3, 3):
+        raise ValueError(f"pose_metrics: K must be (3,3), got {tuple(K.shape)}")
     P, B = model.shape[0], pose_pred.shape[0]
     n = int(_lib.load().rnnpose_pose_metrics_workspace_bytes(B, P)) if symmetric else 0
     ws = torch.empty(max(n, 4) // 4, device=model.device, dtype=F32)
