@@ -865,6 +865,35 @@ int rnnpose_pose_score_f64(const float* rend_depth, const float* rend_desc, cons
                            const int* src_index, int B, int S, int D, int h, int w, int H, int W, double depth_tol, void* workspace,
                            size_t workspace_bytes, double* stats, double* score, rnnpose_stream_t stream);
 
+/* ---- Object onboarding: exact diameter and farthest-point sampling of a point set ----
+ * Both: points (total_points,3) fp32, object b owns the rows [pt_off[b], pt_off[b+1]) (device int32, B+1 entries, the layout of the
+ *   rasteriser and the matcher); an object whose range does not fit the array counts as empty.  All arithmetic fp64 on values
+ *   converted from fp32, without fma contraction: dx = (double)xi - (double)xj, d2 = (dx dx + dy dy) + dz dz.  A point with a
+ *   non-finite coordinate takes part in nothing.  No atomics: bit-identical from run to run and independent of B.  total_points = 0
+ *   is valid (every object empty).  A null pointer, B < 1, total_points < 0, n < 1 or a short workspace return 1 and launch nothing; no
+ *   allocation, no synchronisation.
+ * rnnpose_point_diameter_f64: per object the exact largest pairwise squared distance d2 (B) fp64, diameter (B) = sqrt(d2), the pair
+ *   that attains it, pair (B,2) int32 indices within the object with i < j (ties: the lowest i, then the lowest j), and bounds (B,2,3)
+ *   fp32 the axis-aligned minimum and maximum.  Fewer than two finite points: d2 = diameter = 0, pair = (-1,-1); no finite point:
+ *   bounds = (+inf, -inf).  O(P^2): a tiled upper-triangular sweep (256-point tiles, the j tile in LDS), one partial per tile pair in
+ *   the workspace (rnnpose_point_diameter_workspace_bytes: B * T (T + 1) / 2 * 16 bytes with T = ceil(total_points / 256), 8-byte
+ *   aligned; 0 for a bad size), then one workgroup per object reduces them.  At most 1 048 576 points and 65 535 objects a call.
+ * rnnpose_fps_f64: farthest-point sampling, n picks per object; start (B) device int32.  start[b] >= 0: the first pick is that index
+ *   (an index outside the object, below -1, or of a point that is not finite makes the object empty).  start[b] == -1: the running
+ *   distance starts as every point's squared distance to the origin, so the first pick is the point farthest from the origin.  Every
+ *   later pick is the point with the largest running minimum squared distance to the picks so far, the lowest index on a tie; a
+ *   picked point's running distance becomes -1, so duplicated points come last, lowest index first, and none twice.
+ *   idx (B,n) int32 in pick order; dist2 (B,n) fp64 the running squared distance of each pick when it was picked (+inf for a first
+ *   pick given by start); once an object has nothing left to pick the remaining rows hold idx = -1, dist2 = -1.
+ *   One workgroup of 1024 threads per object, one barrier per pick; objects of up to 8192 points stay in registers, larger ones keep
+ *   their running distances in the workspace (rnnpose_fps_workspace_bytes: one double per point, 8-byte aligned). */
+size_t rnnpose_point_diameter_workspace_bytes(int total_points, int B);
+int rnnpose_point_diameter_f64(const float* points, const int* pt_off, int total_points, int B, void* workspace, size_t workspace_bytes,
+                               double* d2, double* diameter, int* pair, float* bounds, rnnpose_stream_t stream);
+size_t rnnpose_fps_workspace_bytes(int total_points, int B);
+int rnnpose_fps_f64(const float* points, const int* pt_off, int total_points, int B, int n, const int* start, void* workspace,
+                    size_t workspace_bytes, int* idx, double* dist2, rnnpose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,10 @@ PROTOTYPES = {
     "rnnpose_pnp_ransac_topk_f64": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _d, _i, _i, _i, _d, _i, _p, _z, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "rnnpose_pose_score_workspace_bytes": (_z, [_i, _i, _i]),
     "rnnpose_pose_score_f64": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _p, _z, _p, _p, _p]),
+    "rnnpose_point_diameter_workspace_bytes": (_z, [_i, _i]),
+    "rnnpose_point_diameter_f64": (_i, [_p, _p, _i, _i, _p, _z, _p, _p, _p, _p, _p]),
+    "rnnpose_fps_workspace_bytes": (_z, [_i, _i]),
+    "rnnpose_fps_f64": (_i, [_p, _p, _i, _i, _i, _p, _p, _z, _p, _p, _p]),
 }
 
 _lib = None

@@ -23,6 +23,8 @@
 #include "pnp_topk.cuh"
 // the pose confidence, placed the same way
 #include "pose_score.cuh"
+// object onboarding: exact diameter and farthest-point sampling, placed the same way
+#include "model_prep.cuh"
 
 namespace {
 
@@ -569,6 +571,41 @@ int rnnpose_pnp_ransac_topk_f64(const float* X, const float* x, const int* count
                      static_cast<const pnp::HypRec*>(rec), static_cast<const int*>(hyp), T, inlier_mask, n_inliers, final_cost, info, pol);
   hipLaunchKernelGGL(pnp::pnp_topk_dup_kernel, dim3(B), dim3(64), 0, st, Kt, static_cast<const pnp::TopkBox*>(box), static_cast<const double*>(pol),
                      static_cast<const int*>(info), dup_of);
+  return rp::check_launch(fn);
+}
+
+// ---- object onboarding: exact diameter and farthest-point sampling of a point set (csrc/model_prep.cuh) ------------------------------------
+size_t rnnpose_point_diameter_workspace_bytes(int total_points, int B) { return mp::diameter_workspace_bytes(total_points, B); }
+
+int rnnpose_point_diameter_f64(const float* points, const int* pt_off, int total_points, int B, void* workspace, size_t workspace_bytes,
+                               double* d2, double* diameter, int* pair, float* bounds, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_point_diameter_f64";
+  RP_REQUIRE(points && pt_off && workspace && d2 && diameter && pair && bounds, fn, "null pointer");
+  RP_REQUIRE(total_points >= 0 && B > 0 && B < 65536, fn, "bad size");
+  RP_REQUIRE(mp::diameter_workspace_bytes(total_points, B) > 0, fn, "bad size (too large: at most 1 048 576 points a call)");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= mp::diameter_workspace_bytes(total_points, B), fn, "workspace too small");
+  hipStream_t st = rp::as_stream(stream);
+  const long long cap = mp::tile_pairs(mp::tiles_of(total_points));
+  mp::Partial* partial = static_cast<mp::Partial*>(workspace);
+  hipLaunchKernelGGL(mp::mp_diameter_pairs_kernel, dim3(static_cast<unsigned>(cap), B), dim3(256), 0, st, points, pt_off, total_points, cap, partial);
+  hipLaunchKernelGGL(mp::mp_diameter_final_kernel, dim3(B), dim3(256), 0, st, points, pt_off, total_points, cap,
+                     static_cast<const mp::Partial*>(partial), d2, diameter, pair, bounds);
+  return rp::check_launch(fn);
+}
+
+size_t rnnpose_fps_workspace_bytes(int total_points, int B) { return mp::fps_workspace_bytes(total_points, B); }
+
+int rnnpose_fps_f64(const float* points, const int* pt_off, int total_points, int B, int n, const int* start, void* workspace,
+                    size_t workspace_bytes, int* idx, double* dist2, rnnpose_stream_t stream) {
+  const char* fn = "rnnpose_fps_f64";
+  RP_REQUIRE(points && pt_off && start && workspace && idx && dist2, fn, "null pointer");
+  RP_REQUIRE(total_points >= 0 && B > 0 && n > 0, fn, "bad size");
+  RP_REQUIRE(static_cast<long long>(B) * n < (1ll << 31), fn, "bad size (too large)");
+  RP_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, fn, "workspace must be 8-byte aligned");
+  RP_REQUIRE(workspace_bytes >= mp::fps_workspace_bytes(total_points, B), fn, "workspace too small");
+  hipLaunchKernelGGL(mp::mp_fps_kernel, dim3(B), dim3(mp::kFpsThreads), 0, rp::as_stream(stream), points, pt_off, total_points, n, start,
+                     static_cast<double*>(workspace), idx, dist2);
   return rp::check_launch(fn);
 }
 

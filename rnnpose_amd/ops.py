@@ -2333,3 +2333,77 @@ def pose_score(rend_depth, rend_desc, window, desc2d, src_index=None, depth_obs=
     _launch("rnnpose_pose_score_f64", _ptr(rend_depth), _ptr(rend_desc), _ptr(window), _ptr(desc2d), _ptr(depth_obs), _ptr(src_index.dev), B, S,
             DESC_DIM, h, w, H, W, depth_tol, _ptr(ws), n, _ptr(stats), _ptr(score), _stream())
     return stats, score
+
+
+# ---- object onboarding: exact diameter and farthest-point sampling ----------------------------------------------------
+DIAMETER_MAX_POINTS = 1 << 20
+
+
+def _object_offsets(fn, points, pt_off):
+    """points (total,3) and pt_off (None: one object; B+1 host integers, checked here; or a device int32 tensor, taken as it is: the
+    kernels give an object whose range does not fit nothing) -> points (at least one row behind the pointer), total, pt_off on the
+    device, B."""
+    _strict(points, "points", F32, fn)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{fn}: points must be (total, 3), got {tuple(points.shape)}")
+    total, dev = points.shape[0], points.device
+    if isinstance(pt_off, torch.Tensor) and pt_off.is_cuda:
+        _strict(pt_off, "pt_off", torch.int32, fn)
+        if pt_off.dim() != 1 or pt_off.numel() < 2 or pt_off.device != dev:
+            raise ValueError(f"{fn}: pt_off must hold B + 1 offsets on the device of points")
+    else:
+        host = [0, total] if pt_off is None else [int(v) for v in (pt_off.tolist() if hasattr(pt_off, "tolist") else pt_off)]
+        if len(host) < 2 or host[0] < 0 or host[-1] > total or any(b < a for a, b in zip(host, host[1:])):
+            raise ValueError(f"{fn}: pt_off must be B + 1 ascending offsets inside [0, {total}], got {host[:6]}")
+        pt_off = torch.tensor(host, dtype=torch.int32, device=dev)
+    if total == 0:
+        points = torch.zeros(1, 3, device=dev, dtype=F32)              # (a pointer to hand over; total_points stays 0)
+    return points, total, pt_off, pt_off.numel() - 1
+
+
+def point_diameter(points, pt_off=None):
+    """Exact diameter of B point sets (rnnpose_point_diameter_f64).  points (total,3) fp32 on the GPU, object b = rows
+    [pt_off[b], pt_off[b+1]) (None: one object of all rows; B+1 host integers; or a device int32 tensor).
+    -> d2 (B) fp64 the largest pairwise squared distance, diameter (B) fp64, pair (B,2) int32 (i < j, the lowest on ties, (-1,-1) with
+    fewer than two finite points), bounds (B,2,3) fp32 (min, max).  O(P^2) pair evaluations in fp64.
+    Device, dtype, contiguity and the offsets are checked here, on the host (ValueError); nothing is converted."""
+    fn = "point_diameter"
+    points, total, pt_off, B = _object_offsets(fn, points, pt_off)
+    n = int(_lib.load().rnnpose_point_diameter_workspace_bytes(total, B))
+    if n == 0:
+        raise ValueError(f"{fn}: {total} points in {B} objects are more than one call takes ({DIAMETER_MAX_POINTS} points, 65535 objects)")
+    dev = points.device
+    ws = torch.empty(n // 8, device=dev, dtype=F64)
+    d2, diam = torch.empty(B, device=dev, dtype=F64), torch.empty(B, device=dev, dtype=F64)
+    pair, bounds = torch.empty(B, 2, device=dev, dtype=torch.int32), torch.empty(B, 2, 3, device=dev, dtype=F32)
+    _launch("rnnpose_point_diameter_f64", _ptr(points), _ptr(pt_off), total, B, _ptr(ws), n, _ptr(d2), _ptr(diam), _ptr(pair), _ptr(bounds), _stream())
+    return d2, diam, pair, bounds
+
+
+def farthest_points(points, n, pt_off=None, start=-1):
+    """Farthest-point sampling, n picks per object (rnnpose_fps_f64).  points / pt_off as point_diameter; start: one integer for every
+    object, B integers, or a device int32 tensor (B): >= 0 the first pick, -1 the point farthest from the origin (the rule of the
+    reference's fragmentation_fps).
+    -> idx (B,n) int32 in pick order and dist2 (B,n) fp64, the running squared distance of each pick when it was picked (+inf for a given
+    first pick): sqrt(dist2[b][k]) is the coverage radius after k picks.  Rows past the last pickable point hold -1.
+    Device, dtype, contiguity, the offsets and host start values are checked here (ValueError); nothing is converted."""
+    fn = "farthest_points"
+    points, total, pt_off, B = _object_offsets(fn, points, pt_off)
+    n = int(n)
+    if n < 1 or B * n >= 2 ** 31:
+        raise ValueError(f"{fn}: n must be >= 1 and B * n < 2^31, got n = {n}, B = {B}")
+    dev = points.device
+    if isinstance(start, torch.Tensor) and start.is_cuda:
+        _strict(start, "start", torch.int32, fn)
+        if tuple(start.shape) != (B,) or start.device != dev:
+            raise ValueError(f"{fn}: start must be ({B},) on the device of points, got {tuple(start.shape)}")
+    else:
+        host = [int(start)] * B if isinstance(start, int) else [int(v) for v in (start.tolist() if hasattr(start, "tolist") else start)]
+        if len(host) != B or any(v < -1 for v in host):
+            raise ValueError(f"{fn}: start must be {B} integers >= -1, got {host[:6]}")
+        start = torch.tensor(host, dtype=torch.int32, device=dev)
+    nb = int(_lib.load().rnnpose_fps_workspace_bytes(total, B))
+    ws = torch.empty(nb // 8, device=dev, dtype=F64)
+    idx, dist2 = torch.empty(B, n, device=dev, dtype=torch.int32), torch.empty(B, n, device=dev, dtype=F64)
+    _launch("rnnpose_fps_f64", _ptr(points), _ptr(pt_off), total, B, n, _ptr(start), _ptr(ws), nb, _ptr(idx), _ptr(dist2), _stream())
+    return idx, dist2

@@ -18,8 +18,12 @@ from . import ops
 class DescriptorPoseInitializer:
     # `tau` and `min_sim` are STARTING VALUES: no measurement of this project supports them ("not claimed").
     def __init__(self, models, device="cuda", step=2, min_sim=0.5, mutual=True, hypotheses=1024, tau=4.0, n_polish=4, seed=0,
-                 pixel_center=0.5, min_count=4, top_k=1, sep_frac=0.1, min_inliers=0):
-        """top_k, sep_frac, min_inliers: `candidates` returns the top_k best DISTINCT hypotheses (ops.pnp_ransac_topk, DESIGN.md section
+                 pixel_center=0.5, min_count=4, top_k=1, sep_frac=0.1, min_inliers=0, point_subset=None):
+        """point_subset: None, or N: the table of a class with more than N vertices holds only its N farthest-point vertices
+        (ops.farthest_points from the vertex farthest from the origin, computed once per class) and their descriptors, so the matcher's
+        cost no longer grows with the mesh; `point_idx` then indexes that subset and `subset_index[class]` (int64, on the device) maps it
+        back to vertex indices (None for a class that kept all its vertices).  Not tuned.
+        top_k, sep_frac, min_inliers: `candidates` returns the top_k best DISTINCT hypotheses (ops.pnp_ransac_topk, DESIGN.md section
         22; sep_frac is a starting value like tau); `__call__` does not read them.
         hypotheses: log 0.01 / log(1 - w^3) of them give 99 % confidence at inlier ratio w; 1024 covers w >= 0.17 (not tuned).
         seed: the random words of EVERY call come from a torch.Generator on the device re-seeded with it, so a call is a pure
@@ -34,6 +38,10 @@ class DescriptorPoseInitializer:
         self.top_k, self.sep_frac, self.min_inliers = int(top_k), float(sep_frac), int(min_inliers)
         if not 1 <= self.top_k <= ops.PNP_TOPK_MAX or not 0.0 <= self.sep_frac < float("inf") or self.min_inliers < 0:
             raise ValueError(f"top_k in [1,{ops.PNP_TOPK_MAX}], sep_frac >= 0 and finite, min_inliers >= 0")
+        self.point_subset = None if point_subset is None else int(point_subset)
+        if self.point_subset is not None and self.point_subset < 4:
+            raise ValueError("point_subset must be None or >= 4 (a P3P sample needs three matches and the score a fourth)")
+        self.subset_index = {}  # class -> vertex index of every table row (None: the table holds all vertices)
         self._class = {}        # class -> (descriptors (P,32), points (P,3)) on the device
         self._tables = {}       # tuple of names -> (desc3d, points, offsets on the host, offsets on the device)
         self._gen = None
@@ -49,6 +57,12 @@ class DescriptorPoseInitializer:
                     p = torch.as_tensor(np.asarray(m.verts, np.float32)).to(self.device)
                     if d.shape != (p.shape[0], ops.DESC_DIM):
                         raise ValueError(f"class {n}: geofea_3d must hold {ops.DESC_DIM} channels for each of the {p.shape[0]} vertices")
+                    self.subset_index[n] = None
+                    if self.point_subset is not None and p.shape[0] > self.point_subset:
+                        keep = ops.farthest_points(p, self.point_subset, None, -1)[0][0]
+                        keep = keep[keep >= 0].long()
+                        self.subset_index[n] = keep
+                        d, p = d[keep].contiguous(), p[keep].contiguous()
                     self._class[n] = (d, p)
             off = [0]
             for n in names:

@@ -39,6 +39,8 @@ _SCHEMAS = {
     "pnp_ransac": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4) -> (Tensor T, Tensor cost, Tensor inliers, Tensor best, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info)",
     "pnp_ransac_topk": "(Tensor X, Tensor x, Tensor count, Tensor K, Tensor rnd, float tau=4.0, int n_polish=4, int min_count=4, int top_k=4, float sep_frac=0.1, int min_inliers=0) -> (Tensor T, Tensor cost, Tensor inliers, Tensor hyp, Tensor inlier_mask, Tensor n_inliers, Tensor final_cost, Tensor info, Tensor dup_of, Tensor n_found)",
     "pose_score": "(Tensor rend_depth, Tensor rend_desc, Tensor window, Tensor desc2d, Tensor src_index, Tensor? depth_obs=None, float depth_tol=0.015) -> (Tensor stats, Tensor score)",
+    "point_diameter": "(Tensor points, Tensor? pt_off=None) -> (Tensor d2, Tensor diameter, Tensor pair, Tensor bounds)",
+    "farthest_points": "(Tensor points, int n, Tensor? pt_off=None, Tensor? start=None) -> (Tensor idx, Tensor dist2)",
 }
 
 
@@ -150,10 +152,35 @@ def _pose_score(rend_depth, rend_desc, window, desc2d, src_index, depth_obs=None
     return ops.pose_score(rend_depth, rend_desc, window.to(torch.int32).contiguous(), desc2d, src_index, depth_obs, depth_tol)
 
 
+def _host_ints(t):
+    return None if t is None else t.detach().cpu().tolist()
+
+
+def _point_diameter(points, pt_off=None):
+    """pt_off (B+1,): an integer tensor, checked on the host (ValueError) before anything is launched; None: one object."""
+    return ops.point_diameter(points, _host_ints(pt_off))
+
+
+def _farthest_points(points, n, pt_off=None, start=None):
+    """pt_off (B+1,) and start (B,): integer tensors, checked on the host; start None: -1 for every object."""
+    return ops.farthest_points(points, n, _host_ints(pt_off), -1 if start is None else _host_ints(start))
+
+
 # ---- fake (meta) implementations: shapes / dtypes only -----------------------------------------------------------------
 def _f_pose_score(rend_depth, rend_desc, window, desc2d, src_index, depth_obs=None, depth_tol=0.015):
     B = rend_desc.shape[0]
     return rend_desc.new_empty((B, len(ops.POSE_SCORE_COLUMNS)), dtype=torch.float64), rend_desc.new_empty((B,), dtype=torch.float64)
+
+
+def _f_point_diameter(points, pt_off=None):
+    B = 1 if pt_off is None else pt_off.shape[0] - 1
+    e = lambda shape, dt: points.new_empty(shape, dtype=dt)
+    return e((B,), torch.float64), e((B,), torch.float64), e((B, 2), torch.int32), e((B, 2, 3), torch.float32)
+
+
+def _f_farthest_points(points, n, pt_off=None, start=None):
+    B = 1 if pt_off is None else pt_off.shape[0] - 1
+    return points.new_empty((B, n), dtype=torch.int32), points.new_empty((B, n), dtype=torch.float64)
 
 
 def _f_desc_match(desc3d, points, pt_off, desc2d, src_index, bbox, step=2, min_sim=0.5, mutual=True, pixel_center=0.5, M=0):
@@ -260,7 +287,8 @@ def register():
              "zoom_crop": (_zoom_crop, _f_zoom_crop), "raster_occlusion": (_raster_occlusion, _f_raster_occlusion),
              "bop_sym_dist": (_bop_sym_dist, _f_bop_sym_dist), "bop_vsd": (_bop_vsd, _f_bop_vsd),
              "desc_match": (_desc_match, _f_desc_match), "pnp_ransac": (_pnp_ransac, _f_pnp_ransac),
-             "pose_score": (_pose_score, _f_pose_score), "pnp_ransac_topk": (_pnp_ransac_topk, _f_pnp_ransac_topk)}
+             "pose_score": (_pose_score, _f_pose_score), "pnp_ransac_topk": (_pnp_ransac_topk, _f_pnp_ransac_topk),
+             "point_diameter": (_point_diameter, _f_point_diameter), "farthest_points": (_farthest_points, _f_farthest_points)}
     for name, schema in _SCHEMAS.items():
         lib.define(name + schema)
         real, fake = impls[name]
